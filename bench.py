@@ -20,7 +20,14 @@ interior positions are applied while it runs).
                    `weak` (a 64-element-column strip per rank of a (64 N) x 64 mesh)
   --scaling weak   the weak-scaling mesh as the headline instead
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the --steps steps and prints the result line: the headline
+(`value`, `ms_per_step`) and what follows from it without another run.  --full adds everything that takes
+runs of its own: the 1000-launch graph timing, `laplacian_only`, `mfma_variant`, `roofline_hbm`, the other
+meshes (`strong_hbm`, `weak`, `weak_hbm`), `velocity_solve`, `cpu_baseline` and, at N > 1, the roofline of the
+apply alone.  --dump-outputs DIR writes the y of the last timed step as DIR/y.npy (float64; N > 1:
+DIR/y_rank<r>.npy), so that two builds can be compared output for output: the inputs are seeded.
+
+Run:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
       torchrun --nproc-per-node N bench.py --gpus N ...
 Prints ONE JSON line on rank 0.
 """
@@ -72,7 +79,30 @@ def parse():
     ap.add_argument("--vsolve-P", type=int, default=12)
     ap.add_argument("--exchange", default="allreduce", choices=["allreduce", "p2p"],
                     help="interface assembly for N > 1: one RCCL all-reduce, or send/recv with the two neighbours")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (1000-launch graph timing, Laplacian-only and "
+                         "MFMA variants, HBM-regime and other meshes, velocity solve, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output of the last one as DIR/y.npy (N > 1: y_rank<r>.npy)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all ranks' files together
+
+
+def dump_outputs(path, y, world, rank):
+    """The timed path's output (y of the last timed step, as a caller of mesh.apply / StripApply receives it)
+    as float64 .npy.  An output beyond this rank's share of DUMP_LIMIT_BYTES is sampled at fixed, seeded
+    positions (the same ones for every run of the same size)."""
+    os.makedirs(path, exist_ok=True)
+    a = y.detach().cpu().numpy().astype(np.float64, copy=False)
+    cap = DUMP_LIMIT_BYTES // world // 8 - 16   # entries; 128 bytes left for the .npy header
+    if a.size > cap:
+        a = a[np.sort(np.random.default_rng(977).choice(a.size, size=cap, replace=False))]
+    np.save(os.path.join(path, "y.npy" if world == 1 else f"y_rank{rank}.npy"), a)
 
 
 def algorithmic(P, nex, ney):
@@ -368,6 +398,8 @@ def main():
     N_glob = (nex * P + 1) * (ney * P + 1)
     value = N_glob * args.steps / secs
     ms = secs / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, world, rank)
 
     # roofline of the dominant kernel (the fused apply) on this rank
     n_loc = mesh.n_local
@@ -375,18 +407,16 @@ def main():
     apply_only = (lambda: mesh.apply(T, y, **kw))
     # the kernel's average launch duration, measured live: the timed region (HIP events on the launch
     # stream) / launches at N = 1; at N > 1 the step also holds the exchange, so the apply alone is
-    # timed the same way (all launches of one graph).  graph1000_us: 1000 back-to-back launches in one
-    # graph, where the graph-launch cost is fully amortised.
+    # timed the same way (all launches of one graph; a run of its own: --full).  graph1000_us (--full):
+    # 1000 back-to-back launches in one graph, where the graph-launch cost is fully amortised.
     if world == 1:
         kern_s = secs / args.steps
-    else:
+    elif args.full:
         k_secs, _ = time_steps(apply_only, args.steps, args.warmup, dev, use_graph=True)
         kern_s = k_secs / args.steps
-    g1000_us = graph_kernel_us(apply_only, dev)
-    achieved = bytes_launch / kern_s / 1e9
+    else:
+        kern_s = None
     workload = f"cd_matvec_{nex}x{ney}_P{P}"
-    # PMC traffic was measured on the whole-mesh kernel: a strip launch is another workload
-    traffic, traffic_kernel = load_pmc(workload, mesh.kernel_name()) if world == 1 else (None, None)
 
     def regime(n_rank, latency=False):
         mb = 32.0 * n_rank / 1e6
@@ -400,7 +430,7 @@ def main():
         "metric": BASELINE_METRIC,
         "work": "y = K T + Pe (u.Gx T + v.Gy T), Dirichlet identity rows on x=0,1: the Laplacian+convection "
                 "matvec north_star targets (ConvectionDiffusion_Solver.py:104-121); the Laplacian-only K T "
-                "is reported under laplacian_only",
+                "is reported under laplacian_only (--full)",
         "value": value, "unit": "DOF-updates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": ms, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f64",
         "data": "synthetic (T,u,v ~ U(-1,1), default_rng(2024+rank); Pe=40; Dirichlet W/E rows)",
@@ -416,14 +446,21 @@ def main():
                        + (" (RCCL)" if args.dist_backend == "nccl" else " (gloo rehearsal)")
                        if world > 1 else ""),
                    "regime": regime(n_loc, latency=world > 1 and 32.0 * n_loc < 256e6), "hipgraph": use_graph},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_kernel": traffic_kernel,
-                     "kernel": mesh.kernel_name(), "bytes_per_launch": bytes_launch,
-                     "flops_per_launch": flops_launch, "kernel_us": kern_s * 1e6,
-                     "kernel_us_from": "timed region / launches (HIP events on the launch stream)",
-                     "graph1000_us": g1000_us, "frac_graph1000": bytes_launch / (g1000_us * 1e3) / HBM_PEAK_GBS,
-                     "fp64_tflops": flops_launch / kern_s / 1e12, "fp64_peak_tflops": FP64_PEAK_TFLOPS},
     }
+    if kern_s is not None:
+        achieved = bytes_launch / kern_s / 1e9
+        # PMC traffic was measured on the whole-mesh kernel: a strip launch is another workload
+        traffic, traffic_kernel = load_pmc(workload, mesh.kernel_name()) if world == 1 else (None, None)
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_kernel": traffic_kernel,
+                           "kernel": mesh.kernel_name(), "bytes_per_launch": bytes_launch,
+                           "flops_per_launch": flops_launch, "kernel_us": kern_s * 1e6,
+                           "kernel_us_from": "timed region / launches (HIP events on the launch stream)",
+                           "fp64_tflops": flops_launch / kern_s / 1e12, "fp64_peak_tflops": FP64_PEAK_TFLOPS}
+        if args.full:
+            g1000_us = graph_kernel_us(apply_only, dev)
+            out["roofline"].update(graph1000_us=g1000_us,
+                                   frac_graph1000=bytes_launch / (g1000_us * 1e3) / HBM_PEAK_GBS)
 
     if world > 1:
         # the N > 1 headline changed definition in round 5 (rounds 1-4: weak scaling, 64 x 64 elements per
@@ -431,7 +468,7 @@ def main():
         out["headline_definition"] = (f"{args.scaling} scaling of the {nex}x{ney} mesh over {world} GPUs (round 5 on; "
                                       "rounds 1-4 reported weak scaling, 64x64 elements per GPU, as the headline: "
                                       "that is the 'weak' key here)")
-    if world == 1:
+    if args.full and world == 1:
         # BASELINE.json's metric read literally: the Laplacian-only y = K T (16 B/DOF: read T, write y)
         kwl = dict(c_stiff=1.0)
         kl = graph_kernel_us(lambda: mesh.apply(T, y, **kwl), dev) * 1e-6
@@ -450,7 +487,7 @@ def main():
                                "frac_mfma_peak": flops_launch / km / 1e12 / FP64_PEAK_TFLOPS,
                                "flops_per_launch": flops_launch, "speedup_band_over_mfma": km / kern_s}
 
-    if rank == 0 and world == 1 and args.hbm_ne > 0:
+    if args.full and rank == 0 and world == 1 and args.hbm_ne > 0:
         # HBM regime: 1024^2 elements, P=8 (N = 67.1 M, 2.15 GB moved per apply > 256 MB MALL)
         big = get_mesh(P, args.hbm_ne, args.hbm_ne, 1.0 / args.hbm_ne, 1.0 / args.hbm_ne)
         Tb, ub, vb = (torch.rand(big.n_local, dtype=torch.float64, device=dev) * 2 - 1 for _ in range(3))
@@ -473,7 +510,7 @@ def main():
             "bytes_per_launch": bl, "achieved": bl / kbl / 1e9, "unit_bw": "GB/s", "frac": bl / kbl / 1e9 / HBM_PEAK_GBS}
         del Tb, ub, vb, yb
 
-    if args.extra_steps > 0:
+    if args.full and args.extra_steps > 0:
         # the other meshes per rank count (north_star: absolute numbers at 1, 2, 4 and 8 GPUs): the HBM-regime mesh
         # split into N strips, the weak-scaling mesh (or, with --scaling weak, the strong one), and the HBM-regime
         # weak-scaling mesh of SURVEY 8(d) (weak_ne^2 elements per GPU; at N = 1 its baseline)
@@ -499,14 +536,14 @@ def main():
             out["weak_hbm"] = dict(extra(wn * world, wn, 1.0 / wn, 6072 + rank, False), scaling="weak")
             torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and args.vsolve_ne > 0:
+    if args.full and rank == 0 and world == 1 and args.vsolve_ne > 0:
         try:
             out["velocity_solve"] = velocity_solve_line(args.vsolve_ne, args.vsolve_P, dev)
         except (RuntimeError, ValueError) as e:   # an extra key: it never fails the headline line
             out["velocity_solve"] = {"error": str(e)[:300]}
         torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         out["cpu_baseline"] = cpu_baseline(P, ne, Pe, args.cpu_seconds)
         out["speedup_vs_cpu"] = value / out["cpu_baseline"]["value"]
     if rank == 0:

@@ -7,7 +7,7 @@ TAG=${1:-r02}
 O=gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
-BENCH="bench.py --steps 20 --warmup 5"
+BENCH="bench.py --full --steps 20 --warmup 5"
 timeout -k 10 900 python -u -m pytest tests -m gpu -q -p no:cacheprovider -rf --timeout 300 --timeout-method thread \
   > $O/gputests.log 2>&1; rc=$?
 tail -4 $O/gputests.log

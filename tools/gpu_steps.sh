@@ -36,13 +36,13 @@ for s in "$@"; do
     mfmapmc)    tools/pmc_run.sh "$O/pmc_mfma64" -- python tools/kbench.py --meshes 8:64 --reps 200 --algo 2 || exit 1 ;;
     batchedinv) step batchedinv 300 $PYT tests/test_batched_inverse.py tests/test_gpu_dense_inverse.py ;;
     smoke)      step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)      step bench 600 python bench.py ;;
+    bench)      step bench 600 python bench.py --full ;;
     benchgloo)  # the N > 1 bench path (strip partition, interface exchange, max-over-ranks timing) rehearsed with
                 # several ranks on one GPU over gloo (RCCL needs one GPU per rank); all-reduce and p2p exchanges
       for nr in 2 4; do for ex in allreduce p2p; do
         step benchgloo_${nr}_$ex 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $nr \
           --master-addr 127.0.0.1 --master-port 2962$nr bench.py --gpus $nr --steps 20 --warmup 5 \
-          --dist-backend gloo --exchange $ex --cpu-seconds 0 --extra-steps 20
+          --dist-backend gloo --exchange $ex --full --cpu-seconds 0 --extra-steps 20
       done; done ;;
     benchdrv)   step benchdrv 300 python bench.py --gpus 1 --steps 20 --warmup 5 ;;   # the driver's command
     pmccd64)    tools/pmc_run.sh "$O/pmc_cd64" -- python tools/kbench.py --meshes 8:64 --reps 200 || exit 1 ;;
@@ -170,9 +170,9 @@ for s in "$@"; do
       step cfg5part 1080 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
         --master-port 29611 tools/bous_cfg5_solve.py --backend gloo --Ra 1e3 --out "$O/cfg5_part4_ra1e3.json" ;;
     benchtrace)
-      step bench 600 python bench.py
+      step bench 600 python bench.py --full
       step benchtrace 600 rocprofv3 --kernel-trace --stats -d "$O/benchtrace" -o trace --output-format csv -- \
-        python bench.py --cpu-seconds 0 ;;
+        python bench.py --full --cpu-seconds 0 ;;
     bandab)     # every band-kernel variant on the HBM mesh and cfg2 (one process per knob value: read once)
       step bandab_floor 300 python tools/kbench.py --meshes 8:1024 --reps 100 --floor
       for t in 0 1 2 3 4 5 6 7 8 9; do
