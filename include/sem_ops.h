@@ -199,6 +199,29 @@ int sem_apply(sem_handle* h, const sem_apply_desc* d, const double* x, double* y
 /* Name of the kernel sem_apply launches for this handle and algorithm (for profiles / reports). */
 int sem_kernel_name(const sem_handle* h, int algo, char* buf, int len);
 
+/* Fused transposed (adjoint) apply: y = A_D^T z + c_acc * y_in in one launch, for the operator A of
+ * sem_apply_desc, A = c_mass M + c_stiff K + c_gradx diag(cu) G_x + c_grady diag(cv) G_y + diag(d), and
+ * A_D = A with identity Dirichlet rows, so that A_D^T z = A^T ((1 - m) z) + m z for the Dirichlet mask m.
+ * z, y: n_local doubles; z and y must not alias.  Deterministic (fixed summation order, no atomics);
+ * nothing is allocated or synchronised, so the launch can be captured in a graph like sem_apply.
+ * The descriptor is sem_apply_desc unchanged, read as follows:
+ *   c_mass, c_stiff, c_gradx, c_grady, cu, cv   as for sem_apply
+ *   c_extra, ea                                 the diagonal term d = c_extra * ea (none when c_extra == 0 or ea NULL)
+ *   eb, ec, ed                                  must be NULL
+ *   c_acc                                       accumulates on EVERY row, Dirichlet rows included
+ *   dir_mode                                    SEM_DIR_NONE or SEM_DIR_IDENTITY
+ *   dir_mask, dir_sides                         as for sem_apply
+ *   dir_val                                     must be NULL
+ *   algo                                        SEM_ALGO_AUTO only
+ * SEM_EINVAL: SEM_DIR_REPLACE, non-NULL eb / ec / ed / dir_val, z == y, null pointers.
+ * SEM_EUNSUPPORTED: a strip handle (ex_begin != 0 or ex_end != nex), pos_end != 0, an algo other than
+ * SEM_ALGO_AUTO, P outside the compiled range, or a mesh past the band kernel's 32-bit buffer-offset
+ * limit (n_local + (P + 1) N_y >= 2^28). */
+int sem_apply_transpose(sem_handle* h, const sem_apply_desc* d, const double* z, double* y, void* stream);
+
+/* Name of the kernel sem_apply_transpose launches for this handle (for profiles / reports). */
+int sem_transpose_kernel_name(const sem_handle* h, char* buf, int len);
+
 /* SEM.scatter (SEM.py:149-167): u_e[m][n][i][j] = u[global_index(m,n,i,j)] for the
  * local elements; u_e has (ex_end-ex_begin)*ney*(P+1)^2 doubles. */
 int sem_gather_elements(sem_handle* h, const double* u, double* u_e, void* stream);
@@ -215,6 +238,18 @@ int sem_dss(sem_handle* h, const double* a_e, double* a, void* stream);
  * element is not held locally are left untouched.  All pointers are device pointers. */
 int sem_eval_interpolation(sem_handle* h, const double* u_e, int na, const int* m_idx, const double* Sx, int nb,
                            const int* n_idx, const double* Sy, double* out, void* stream);
+
+/* Transpose of sem_eval_interpolation with respect to u_e (whole-mesh handles):
+ *   u_e_bar[m][n][k][l] = sum_{a: m_idx[a] = m} sum_{b: n_idx[b] = n} Sx[a][k] Sy[b][l] out_bar[a*nb+b].
+ * The plot rows of every element column and the plot columns of every element row come as CSR-style
+ * lists built by the host: a_list[a_ptr[m] .. a_ptr[m+1]) = the rows a with m_idx[a] = m in ascending
+ * order (a_ptr has nex + 1 entries), b_list / b_ptr (ney + 1 entries) likewise for the columns.  Points
+ * outside the mesh (index -1) are in no list and contribute nothing; elements without points get 0.
+ * Every entry of u_e_bar (nex*ney*(P+1)^2 doubles) is written by one thread that sums a, then b, in
+ * list order: deterministic, no atomics.  All pointers are device pointers. */
+int sem_eval_interpolation_adjoint(sem_handle* h, const double* out_bar, int na, const int* a_ptr, const int* a_list,
+                                   const double* Sx, int nb, const int* b_ptr, const int* b_list, const double* Sy,
+                                   double* u_e_bar, void* stream);
 
 /* ---- multi-GPU interface lines (element-strip partition) --------------- */
 /* Pack the local partial sums on the two interface lines into buf[(G-1)*NY]

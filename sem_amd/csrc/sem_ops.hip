@@ -42,6 +42,8 @@ static bool band_fits(const sem_handle* h) { return h->n_local + (h->P + 1) * h-
 std::string band_kernel_name(int P, long long n_local);
 int launch_apply_bmfma(const ApplyArgs& a, const sem_handle* h, hipStream_t s);  // apply_band.hip
 std::string bmfma_kernel_name(int P);
+int launch_apply_transpose(const ApplyArgs& a, const sem_handle* h, hipStream_t s);  // apply_transpose.hip
+std::string transpose_kernel_name(int P);
 
 static int hip_check(hipError_t e, const char* what) {
   if (e == hipSuccess) return SEM_OK;
@@ -977,6 +979,32 @@ __global__ void interp_kernel(const double* __restrict__ ue, int P, int ney, int
   }
 }
 
+// Transpose of interp_kernel with respect to u_e: one thread per entry (m, n, k, l) of u_e_bar sums the plot
+// rows of element column m (a_list, ascending) and the plot columns of element row n (b_list, ascending).
+__global__ void interp_adjoint_kernel(const double* __restrict__ ob, int P, int ney, const int* __restrict__ ap,
+                                      const int* __restrict__ al, const double* __restrict__ Sx,
+                                      const int* __restrict__ bp, const int* __restrict__ bl,
+                                      const double* __restrict__ Sy, int nb, double* __restrict__ ueb, int64_t total) {
+  const int n = P + 1;
+  for (int64_t t = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; t < total;
+       t += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int l = static_cast<int>(t % n), k = static_cast<int>((t / n) % n);
+    const int64_t el = t / (n * n);
+    const int e = static_cast<int>(el % ney), m = static_cast<int>(el / ney);
+    double s = 0.0;
+    for (int ia = ap[m]; ia < ap[m + 1]; ++ia) {
+      const int a = al[ia];
+      double r = 0.0;
+      for (int ib = bp[e]; ib < bp[e + 1]; ++ib) {
+        const int b = bl[ib];
+        r = fma(Sy[static_cast<int64_t>(b) * n + l], ob[static_cast<int64_t>(a) * nb + b], r);
+      }
+      s = fma(Sx[static_cast<int64_t>(a) * n + k], r, s);
+    }
+    ueb[t] = s;
+  }
+}
+
 static unsigned grid_for(int64_t total, int threads) {
   int64_t g = (total + threads - 1) / threads;
   return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(g, 65536)));
@@ -1236,6 +1264,60 @@ int sem_apply(sem_handle* h, const sem_apply_desc* d, const double* x, double* y
   }
 }
 
+int sem_apply_transpose(sem_handle* h, const sem_apply_desc* d, const double* z, double* y, void* stream) {
+  if (!h || !d) return set_error(SEM_EINVAL, "null handle or descriptor");
+  if (!z || !y) return set_error(SEM_EINVAL, "null z or y");
+  if (z == y) return set_error(SEM_EINVAL, "z and y must not alias");
+  if (d->dir_mode != SEM_DIR_NONE && d->dir_mode != SEM_DIR_IDENTITY)
+    return set_error(SEM_EINVAL, "the transposed apply takes SEM_DIR_NONE or SEM_DIR_IDENTITY");
+  if (d->eb || d->ec || d->ed) return set_error(SEM_EINVAL, "the transposed apply takes no eb / ec / ed (d = c_extra * ea)");
+  if (d->dir_val) return set_error(SEM_EINVAL, "the transposed apply takes no dir_val");
+  if (h->ex_begin != 0 || h->ex_end != h->nex)
+    return set_error(SEM_EUNSUPPORTED, "the transposed apply is implemented for whole-mesh handles only");
+  if (d->pos_end != 0) return set_error(SEM_EUNSUPPORTED, "the transposed apply has no element-position ranges");
+  if (d->algo != SEM_ALGO_AUTO) return set_error(SEM_EUNSUPPORTED, "the transposed apply has one kernel (SEM_ALGO_AUTO)");
+  if (h->P < 1 || h->P > kMaxOrder) return set_error(SEM_EUNSUPPORTED, "polynomial order outside compiled range");
+  // the kernel addresses the vectors with 32-bit byte offsets, like the band kernel
+  if (!band_fits(h)) return set_error(SEM_EUNSUPPORTED, "the transposed apply needs n_local + (P+1) N_y < 2^28");
+  if (int st = on_device(h)) return st;
+  ApplyArgs a{};
+  a.x = z;
+  a.y = y;
+  a.cu = d->cu;
+  a.cv = d->cv;
+  a.ea = d->ea;
+  a.mask = d->dir_mask;
+  a.cM = d->c_mass;
+  a.cK = d->c_stiff;
+  a.cX = d->c_gradx;
+  a.cY = d->c_grady;
+  a.cE = d->ea ? d->c_extra : 0.0;
+  a.cA = d->c_acc;
+  a.sx = h->dy / h->dx;
+  a.sy = h->dx / h->dy;
+  a.hx = h->dx / 2.0;
+  a.hy = h->dy / 2.0;
+  a.hxy = (h->dx / 2.0) * (h->dy / 2.0);
+  a.NY = h->NY;
+  a.NXg = h->NX;
+  a.line_begin = h->line_begin;
+  a.line_end = h->line_end;
+  a.nex = h->nex;
+  a.ney = h->ney;
+  a.ex_begin = h->ex_begin;
+  a.ex_end = h->ex_end;
+  a.dir_mode = d->dir_mode;
+  a.sides = d->dir_sides;
+  a.n_local32 = static_cast<int>(h->n_local);
+  return launch_apply_transpose(a, h, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sem_transpose_kernel_name(const sem_handle* h, char* buf, int len) {
+  if (!h || !buf || len < 1) return set_error(SEM_EINVAL, "bad arguments");
+  std::snprintf(buf, static_cast<size_t>(len), "%s", transpose_kernel_name(h->P).c_str());
+  return SEM_OK;
+}
+
 int sem_kernel_name(const sem_handle* h, int algo, char* buf, int len) {
   if (!h || !buf || len < 1) return set_error(SEM_EINVAL, "bad arguments");
   std::string name;
@@ -1289,6 +1371,24 @@ int sem_eval_interpolation(sem_handle* h, const double* ue, int na, const int* m
                      reinterpret_cast<hipStream_t>(stream), ue, h->P, h->ney, h->ex_begin, h->ex_end, m_idx, Sx, na,
                      n_idx, Sy, nb, out);
   return hip_check(hipGetLastError(), "interpolation launch");
+}
+
+int sem_eval_interpolation_adjoint(sem_handle* h, const double* out_bar, int na, const int* a_ptr, const int* a_list,
+                                   const double* Sx, int nb, const int* b_ptr, const int* b_list, const double* Sy,
+                                   double* u_e_bar, void* stream) {
+  if (!h || !u_e_bar || na < 0 || nb < 0) return set_error(SEM_EINVAL, "bad interpolation arguments");
+  if (!a_ptr || !b_ptr) return set_error(SEM_EINVAL, "null interpolation row / column list");  // empty lists may be null
+  if ((na > 0 && nb > 0 && !out_bar) || (na > 0 && !Sx) || (nb > 0 && !Sy))
+    return set_error(SEM_EINVAL, "null interpolation table");
+  if (h->ex_begin != 0 || h->ex_end != h->nex)
+    return set_error(SEM_EUNSUPPORTED, "the transposed interpolation is implemented for whole-mesh handles only");
+  if (int st = on_device(h)) return st;
+  const int n = h->P + 1;
+  const int64_t total = static_cast<int64_t>(h->nex) * h->ney * n * n;
+  hipLaunchKernelGGL(interp_adjoint_kernel, dim3(grid_for(total, 256)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), out_bar, h->P, h->ney, a_ptr, a_list, Sx, b_ptr, b_list, Sy,
+                     nb, u_e_bar, total);
+  return hip_check(hipGetLastError(), "transposed interpolation launch");
 }
 
 static int iface_slots(const sem_handle* h, const int* bounds, int G, int* left, int* right) {

@@ -100,6 +100,35 @@ class Mesh:
         _lib.check(self._lib.sem_apply(self._h, C.byref(d), _ptr(x), _ptr(y), self.stream_ptr(stream)))
         return y
 
+    def apply_transpose(self, z, y=None, *, c_mass=0.0, c_stiff=0.0, c_gradx=0.0, c_grady=0.0, cu=None, cv=None,
+                        diag=None, c_acc=0.0, dir_mode=_lib.DIR_NONE, dir_mask=None, dir_sides=0, stream=None,
+                        eb=None, ec=None, ed=None, dir_val=None, algo=_lib.ALGO_AUTO, pos=None):
+        """Fused transposed apply (include/sem_ops.h, sem_apply_transpose): y = A_D^T z + c_acc y for
+        A = c_mass M + c_stiff K + c_gradx diag(cu) G_x + c_grady diag(cv) G_y + diag(diag) and identity
+        Dirichlet rows.  One launch; whole-mesh handles only.  eb, ec, ed, dir_val, algo and pos are the
+        remaining descriptor fields: the transposed apply takes none of them and the library refuses
+        them as the header documents (ValueError / RuntimeError)."""
+        z = self._vec(z, "z")
+        if y is None:
+            y = torch.empty_like(z)
+        self._vec(y, "y")
+        for nm, t in (("cu", cu), ("cv", cv), ("diag", diag), ("eb", eb), ("ec", ec), ("ed", ed), ("dir_val", dir_val)):
+            self._vec(t, nm)
+        if dir_mask is not None:
+            if dir_mask.dtype != torch.uint8 or dir_mask.device != self.device or dir_mask.numel() != self.n_local:
+                raise ValueError("dir_mask must be a uint8 tensor of n_local entries on the mesh device")
+        d = _lib.SemApplyDesc(float(c_mass), float(c_stiff), float(c_gradx), float(c_grady), _ptr(cu), _ptr(cv),
+                              1.0 if diag is not None else 0.0, _ptr(diag), _ptr(eb), _ptr(ec), _ptr(ed), float(c_acc),
+                              int(dir_mode), _ptr(dir_mask), _ptr(dir_val), int(dir_sides), int(algo),
+                              *((0, 0) if pos is None else (int(pos[0]), int(pos[1]))))
+        _lib.check(self._lib.sem_apply_transpose(self._h, C.byref(d), _ptr(z), _ptr(y), self.stream_ptr(stream)))
+        return y
+
+    def transpose_kernel_name(self):
+        buf = C.create_string_buffer(128)
+        _lib.check(self._lib.sem_transpose_kernel_name(self._h, buf, 128))
+        return buf.value.decode()
+
     def kernel_name(self, algo=_lib.ALGO_AUTO):
         buf = C.create_string_buffer(128)
         _lib.check(self._lib.sem_kernel_name(self._h, int(algo), buf, 128))

@@ -106,19 +106,42 @@ class SEMOperator:
         return self.mesh.apply(x, y, c_mass=self.cM, c_stiff=self.cK, c_gradx=cX, cu=cu, c_grady=cY, cv=cv,
                                c_extra=1.0 if d is not None else 0.0, ea=d, eb=x if d is not None else None, **kw)
 
-    def __matmul__(self, x):
+    def apply_transpose(self, x, y=None, **kw):
+        """Device apply of the transpose, A^T x, in one fused launch (sem_apply_transpose): x, y float64
+        tensors on the mesh device; kw = Dirichlet / accumulate options of Mesh.apply_transpose."""
+        cX, cu, cY, cv, d = self._coeffs()
+        return self.mesh.apply_transpose(x, y, c_mass=self.cM, c_stiff=self.cK, c_gradx=cX, cu=cu, c_grady=cY, cv=cv,
+                                         diag=d, **kw)
+
+    def _mul_vec(self, x, apply):
         if isinstance(x, torch.Tensor):
             if x.dim() != 1:
                 return NotImplemented
-            return self.apply(self.mesh.to_device(x))
+            return apply(self.mesh.to_device(x))
         x = np.asarray(x)
         if x.ndim != 1:
             return NotImplemented
         if x.shape[0] != self.shape[1]:
             raise ValueError(f"dimension mismatch: operator {self.shape} @ vector {x.shape}")
-        return self.apply(self.mesh.to_device(x)).cpu().numpy()
+        return apply(self.mesh.to_device(x)).cpu().numpy()
+
+    def __matmul__(self, x):
+        return self._mul_vec(x, self.apply)
 
     dot = __matmul__
+
+    def rmatvec(self, x):
+        """A^T x (SciPy's LinearOperator / sparse-matrix protocol; accepts (N,) or (N, 1))."""
+        if isinstance(x, np.ndarray) and x.ndim == 2 and x.shape[1] == 1:
+            return self.rmatvec(x[:, 0])[:, None]
+        return self._mul_vec(x, self.apply_transpose)
+
+    def transpose(self):
+        """The transposed operator as a thin view (what `csr.T` / `csr.transpose()` give the reference's
+        consumers): `A.T @ x` is one fused launch, nothing is assembled."""
+        return TransposedOperator(self)
+
+    T = property(transpose)
 
     def matvec(self, x):
         """SciPy LinearOperator protocol (accepts (N,) or (N, 1))."""
@@ -214,6 +237,50 @@ def _element_triplets(table, P, e_lo, e_hi, g_lo):
     ii, kk = np.nonzero(table)
     base = np.arange(e_lo, e_hi)[:, None] * P - g_lo
     return (base + ii).ravel(), (base + kk).ravel(), np.tile(table[ii, kk], e_hi - e_lo)
+
+
+class TransposedOperator:
+    """`A.T` of a SEMOperator: a view, not a copy.  `@`, `dot`, `matvec` apply A^T (sem_apply_transpose)
+    with SEMOperator.__matmul__'s conventions for NumPy vectors and device tensors; `rmatvec` is the
+    forward apply; `.T` gives the original operator back.  Operator algebra is not provided on the view:
+    build the sum first and transpose it."""
+    __array_priority__ = 100
+
+    def __init__(self, op):
+        self.op = op
+        self.shape = (op.shape[1], op.shape[0])
+        self.dtype = op.dtype
+
+    def apply(self, x, y=None, **kw):
+        return self.op.apply_transpose(x, y, **kw)
+
+    def __matmul__(self, x):
+        return self.op._mul_vec(x, self.op.apply_transpose)
+
+    dot = __matmul__
+
+    def matvec(self, x):
+        return self.op.rmatvec(x)
+
+    def rmatvec(self, x):
+        return self.op.matvec(x)
+
+    def transpose(self):
+        return self.op
+
+    T = property(transpose)
+
+    def diagonal(self):
+        return self.op.diagonal()
+
+    def tocsr(self):
+        return self.op.tocsr().T.tocsr()
+
+    def toarray(self):
+        return self.tocsr().toarray()
+
+    def __repr__(self):
+        return f"<transpose of {self.op!r}>"
 
 
 class RowRestricted:

@@ -87,6 +87,20 @@ def transfer(field, src, dst):
         f_func=lambda x, y: np.asarray(src._get_interpol(field, np.reshape((x, y), grid))).flatten())
 
 
+def transfer_T(field_bar, src, dst):
+    """The exact transpose of `transfer`: for field_bar on dst's nodes (length dst.N) the vector g of
+    length src.N with <transfer(f, src, dst), field_bar> = <f, g> for every f.  The adjoint of the
+    element interpolation (sem_eval_interpolation_adjoint) gives one value per element copy of a src
+    node; SEM.assemble (direct-stiffness summation) sums the copies -- the transpose of SEM.scatter."""
+    from .. import SEM
+    from ..interp import eval_interpolation_adjoint
+    grid = (2, dst._P * dst._N_ex + 1, dst._P * dst._N_ey + 1)
+    pts = np.reshape((dst.points[0], dst.points[1]), grid)
+    f_e_bar = eval_interpolation_adjoint(np.reshape(np.asarray(field_bar, dtype=np.float64), grid[1:]),
+                                         src.points_e, pts)
+    return SEM.assemble(f_e_bar)
+
+
 def _fwd_only(mode):
     if mode != 'fwd':
         raise ValueError('only forward mode implemented')
@@ -98,6 +112,15 @@ class ConvectionDiffusion_Component(_Base):
     def initialize(self):
         self.options.declare('solver_CD', desc='convection-diffusion solver object')
         self.options.declare('solver_NS', desc='NAVIER-STOKES solver object')
+        # not in the reference (whose components are forward-mode only): opt in to reverse mode
+        self.options.declare('adjoint', default=False, desc="also implement mode='rev' (adjoint derivatives)")
+
+    def _rev(self, mode):
+        """True for mode='rev' with adjoint=True; anything but 'fwd' raises as the reference otherwise."""
+        if mode == 'rev' and self.options['adjoint']:
+            return True
+        _fwd_only(mode)
+        return False
 
     def setup(self):
         self.cd, self.ns = self.options['solver_CD'], self.options['solver_NS']
@@ -120,14 +143,30 @@ class ConvectionDiffusion_Component(_Base):
         self.cd._calc_jacobians(outputs['T_cd'])
 
     def apply_linear(self, inputs, outputs, d_inputs, d_outputs, d_residuals, mode, *args):
-        """(:44-49) forward mode only; an absent d_outputs['T_cd'] counts as zero."""
-        _fwd_only(mode)
+        """(:44-49) forward mode; an absent d_outputs['T_cd'] counts as zero.  With adjoint=True also
+        mode='rev' (OpenMDAO's convention: accumulate into the entries that are present):
+        d_outputs['T_cd'] += A_D^T w, d_inputs['u_ns'] += transfer^T (J_u^T w), likewise v_ns, for
+        w = d_residuals['T_cd']."""
+        if self._rev(mode):
+            dT_bar, du_bar, dv_bar = self.cd._get_dresiduals_T(np.asarray(d_residuals['T_cd'], dtype=np.float64))
+            if 'T_cd' in d_outputs:
+                d_outputs['T_cd'] += dT_bar
+            if 'u_ns' in d_inputs:
+                d_inputs['u_ns'] += transfer_T(du_bar, self.ns, self.cd)
+            if 'v_ns' in d_inputs:
+                d_inputs['v_ns'] += transfer_T(dv_bar, self.ns, self.cd)
+            return
         dT = d_outputs['T_cd'] if 'T_cd' in d_outputs else np.zeros(self.cd.N)
         d_residuals['T_cd'] = self.cd._get_dresiduals(dT, *self.change_inputs(d_inputs['u_ns'], d_inputs['v_ns']))
 
     def solve_linear(self, d_outputs, d_residuals, mode):
-        """(:51-57) one Newton update from the current d_outputs as initial guess."""
-        _fwd_only(mode)
+        """(:51-57) one Newton update from the current d_outputs as initial guess.  With adjoint=True
+        also mode='rev': d_residuals['T_cd'] = the solution of A_D^T lambda = d_outputs['T_cd']."""
+        if self._rev(mode):
+            d_residuals['T_cd'] = self.cd._get_update_T(
+                d_outputs['T_cd'], dres0=d_residuals['T_cd'] if 'T_cd' in d_residuals else None)
+            self.iter_count_solve += 1
+            return
         d_outputs['T_cd'] = self.cd._get_update(d_residuals['T_cd'], dT0=d_outputs['T_cd'])
         self.iter_count_solve += 1
 

@@ -146,6 +146,7 @@ class ConvectionDiffusionSolver:
         self._Sys = None
         self._Jac_T_u = None
         self._Jac_T_v = None
+        self._free = None       # 1 - Dirichlet mask as a device vector (_get_dresiduals_T)
 
         # Dirichlet values and mask (ConvectionDiffusion_Solver.py:62-71)
         self._dirichlet = np.full(self.N, np.nan)
@@ -212,6 +213,59 @@ class ConvectionDiffusionSolver:
             kw = dict(c_extra=1.0, ea=ju, eb=self._dev(du), ec=jv, ed=self._dev(dv))
         y = self._apply(self._dev(dT), dir_mode=_lib.DIR_IDENTITY, **self._sys_kw(), **self._dir.kw(), **kw)
         return self._out(y, dT)
+
+    def _whole_mesh_only(self, what):
+        if self._part is not None:
+            raise ValueError(f"ConvectionDiffusion: {what} is implemented for whole-mesh solvers only "
+                             "(no transposed strip apply)")
+
+    def _apply_T(self, w, y=None, **kw):
+        """A_D^T w: one fused transposed launch of Sys with identity Dirichlet rows."""
+        return self._mesh.apply_transpose(w, y, dir_mode=_lib.DIR_IDENTITY, **self._sys_kw(), **self._dir.kw(), **kw)
+
+    def _get_dresiduals_T(self, dres_bar):
+        """Transpose of _get_dresiduals(dT, du, dv): (dT_bar, du_bar, dv_bar) with
+        dT_bar = A_D^T dres_bar, du_bar = (Pe G_x T) (1 - m) dres_bar, dv_bar = (Pe G_y T) (1 - m) dres_bar
+        (m = the Dirichlet mask), so that <_get_dresiduals(dT, du, dv), w> = <dT, dT_bar> + <du, du_bar> +
+        <dv, dv_bar>.  Needs _get_residuals and _calc_jacobians, like the forward method."""
+        self._whole_mesh_only("_get_dresiduals_T")
+        if self._Sys is None or self._Jac_T_u is None:
+            raise RuntimeError("ConvectionDiffusion: _get_residuals and _calc_jacobians must run before "
+                               "_get_dresiduals_T")
+        w = self._dev(dres_bar)
+        if self._free is None:   # 1 - m on the device
+            self._free = self._mesh.to_device((~self._dir.mask_np).astype(np.float64))
+        wf = self._free * w
+        out = (self._apply_T(w), self._Jac_T_u._coeffs()[4] * wf, self._Jac_T_v._coeffs()[4] * wf)
+        return tuple(self._out(y, dres_bar) for y in out)
+
+    def _get_update_T(self, dT_bar, dres0=None):
+        """Adjoint of the Newton update: solve A_D^T lambda = dT_bar with the device GMRES, every
+        iteration one fused transposed apply.  Stopping rule and restart are the forward solve's
+        (atol = mtol sqrt(N), rtol = 0, restart = min(int(0.3 N), max_basis)).  Unpreconditioned: the
+        condensed direct factor solves with A_D, not with its transpose."""
+        self._whole_mesh_only("_get_update_T")
+        if self._Sys is None:
+            raise RuntimeError("ConvectionDiffusion: _get_residuals must run before _get_update_T")
+        b = self._dev(dT_bar)
+        x0 = self._dev(dres0)
+        it = [0]
+
+        def cb(est):
+            it[0] += 1
+            if "LGMRES_iter" in self._iprint:
+                print(f"ConvectionDiffusion adjoint GMRES: {it[0]}\t{est}", flush=True)
+
+        restart = max(1, min(int(self.N * 0.3), self._max_basis))
+        r = gmres(lambda v: self._apply_T(v), b, x0=x0, atol=self._mtol * np.sqrt(self.N), rtol=0.0, restart=restart,
+                  maxiter=10 * self.N, callback=cb)
+        if r.info != 0:
+            raise RuntimeError(f"ConvectionDiffusion LGMRES: Failed to converge in {r.info} iterations")
+        self.matvecs = r.matvecs
+        if "LGMRES_suc" in self._iprint:
+            res = (self._apply_T(r.x) - b).abs().max().item()
+            print(f"ConvectionDiffusion adjoint GMRES: Converged in {r.matvecs} evaluations with max-norm {res}")
+        return self._out(r.x, dT_bar)
 
     def _get_update(self, dres, dT0=None):
         """Newton update: solve dres_op(dT) = dres (ConvectionDiffusion_Solver.py:123-156)."""
