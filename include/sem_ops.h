@@ -60,7 +60,7 @@ enum sem_dir_mode {
 enum sem_algo {
   SEM_ALGO_AUTO = 0,
   SEM_ALGO_VALU = 1,   /* two-phase VALU tile kernel (x and y contractions in separate passes)   */
-  SEM_ALGO_MFMA = 2,   /* fp64 MFMA (v_mfma_f64_16x16x4_f64) element-block contractions, P <= 15 */
+  SEM_ALGO_MFMA = 2,   /* band-form fp64 MFMA kernel (v_mfma_f64_16x16x4_f64), P <= 16            */
   SEM_ALGO_COLUMN = 3, /* single-phase VALU column kernel                                         */
   SEM_ALGO_BAND = 4    /* assembled-band VALU kernel: one banded dot product per node and direction,
                           x / y roles on separate waves, wave-uniform compile-time coefficients   */
@@ -138,7 +138,7 @@ enum sem_tune {
   SEM_TUNE_RETIRED_1 = 1,
   SEM_TUNE_BAND_KP = 2,   /* SEM_BAND_KP: -1 = struct-only kernel arguments, else preloaded (bitwise) */
   SEM_TUNE_RETIRED_3 = 3,
-  SEM_TUNE_MFMA_TILE = 4, /* SEM_MFMA_TILE: 0 = band-form MFMA kernel; 3 = element-block MFMA (round 4) */
+  SEM_TUNE_MFMA_TILE = 4, /* SEM_MFMA_TILE: 0 = band-form MFMA kernel; 3 = element-block MFMA (round 4), P <= 15 */
   SEM_TUNE_RETIRED_5 = 5,
   SEM_TUNE_NS_APPLY = 6,  /* SEM_NS_APPLY: 1 = sem_ns_apply's LDS-tile form instead of the band form
                            * (agree to rounding, not bitwise)                                         */
@@ -196,7 +196,8 @@ int sem_get_info(const sem_handle* h, sem_info* out);
 /* Fused matrix-free operator apply (see sem_apply_desc).  x, y: n_local doubles. */
 int sem_apply(sem_handle* h, const sem_apply_desc* d, const double* x, double* y, void* stream);
 
-/* Name of the kernel sem_apply launches for this handle and algorithm (for profiles / reports). */
+/* Name of the kernel sem_apply launches for this handle and algorithm without a position range (for
+ * profiles / reports); for a pair sem_apply refuses, the status and message sem_apply returns. */
 int sem_kernel_name(const sem_handle* h, int algo, char* buf, int len);
 
 /* Fused transposed (adjoint) apply: y = A_D^T z + c_acc * y_in in one launch, for the operator A of

@@ -29,14 +29,10 @@
 // Barriers: staged tile in LDS -> X and Y contractions run concurrently -> X epilogue.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdlib>
-#include <string>
-
 #include "apply_common.h"
+#include "apply_select.h"
 
 namespace sem {
-
 
 // ---- Even-odd (centro-symmetric) form of one element's rows.
 // G_s is exactly centro-antisymmetric (G[P-i][P-l] = -G[i][l], GLL.py:62-70); K_s is
@@ -745,17 +741,6 @@ __global__ __launch_bounds__((BCfg<P, TXE, TYE, NS>::THREADS)) void apply_band_k
                                                     pnbytes, a);
 }
 
-static int hip_check_b(hipError_t e, const char* what) {
-  if (e == hipSuccess) return SEM_OK;
-  return set_error(SEM_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-// Default cache policy (measured in-process, tools/ab_env.py, profiles/r01/band/cpol_ab.txt): on a mesh
-// whose working set stays in the MALL, system-scope y stores (sc0 sc1: written through L2 as they
-// are issued) save the end-of-kernel L2 writeback, 4.66 -> 4.38 us at cfg2; on HBM-sized meshes
-// that costs ~1 %, and non-temporal u, v loads (read once) are neutral to slightly better.
-static int band_cpol(long long n_local) { return 32LL * n_local < (128LL << 20) ? 3 : 256; }
-
 // The kernel arguments every band-family launch shares (apply_band, apply_bmfma): pointers, fused factors,
 // the strip and the Dirichlet fields; the launch sets its grid fields.
 static BandArgs band_args(const ApplyArgs& g) {
@@ -827,7 +812,7 @@ static int launch_band(const ApplyArgs& g, const sem_handle* h, hipStream_t s) {
     else
       hipLaunchKernelGGL((apply_band_kp<P, TXE, TYE, NS, false, CM, false>), grid, block, 0, s, SEM_KP_ARGS);
 #undef SEM_KP_ARGS
-    return hip_check_b(hipGetLastError(), "apply (band) launch");
+    return hip_check(hipGetLastError(), "apply (band) launch");
   }
   if (full && grad)
     hipLaunchKernelGGL((apply_band<P, TXE, TYE, NS, true, CM, true>), grid, block, 0, s, b);
@@ -837,7 +822,7 @@ static int launch_band(const ApplyArgs& g, const sem_handle* h, hipStream_t s) {
     hipLaunchKernelGGL((apply_band<P, TXE, TYE, NS, false, CM, true>), grid, block, 0, s, b);
   else
     hipLaunchKernelGGL((apply_band<P, TXE, TYE, NS, false, CM, false>), grid, block, 0, s, b);
-  return hip_check_b(hipGetLastError(), "apply (band) launch");
+  return hip_check(hipGetLastError(), "apply (band) launch");
 }
 
 // =========================================================================== band-form MFMA kernel
@@ -865,12 +850,12 @@ typedef double dbl4v __attribute__((ext_vector_type(4)));
 
 template <int P>
 struct BMCfg {
-  static constexpr int TXE = 16 / P > 0 ? 16 / P : 1;
+  static constexpr int TXE = bmfma_txe(P);
   static constexpr int RX = TXE * P;                       // output lines per tile (<= 16)
   static constexpr int CB = RX;                            // output columns per block (element aligned)
   static constexpr int KS = (RX + P + 1 + 3) / 4;          // k-steps of the (RX + P + 1)-wide window
   static constexpr int KW = 4 * KS;
-  static constexpr int NB = 4;                             // column blocks (= waves) per tile
+  static constexpr int NB = kBmfmaNB;                      // column blocks (= waves) per tile
   static constexpr int THREADS = 64 * NB;
   static constexpr int SL = KW > P + 16 ? KW : P + 16;     // staged lines from gx0 - P (y product reads P .. P + 15)
   static constexpr int SC0 = (NB - 1) * CB + KW, SC1 = P + (NB - 1) * CB + 16;
@@ -1117,7 +1102,6 @@ __global__ __launch_bounds__(BMCfg<P>::THREADS) void apply_bmfma(const BandArgs 
 template <int P>
 static int launch_bmfma(const ApplyArgs& g, const sem_handle* h, hipStream_t s) {
   using C = BMCfg<P>;
-  if (g.pos1 > 0) return set_error(SEM_EUNSUPPORTED, "element-position ranges are implemented by the band kernel only");
   const long long nlines = static_cast<long long>(h->ex_end - h->ex_begin) * P + 1;
   const long long tiles_x = (nlines + C::RX - 1) / C::RX;
   const long long tiles_y = (h->NY + C::NB * C::CB - 1) / (C::NB * C::CB);
@@ -1137,71 +1121,22 @@ static int launch_bmfma(const ApplyArgs& g, const sem_handle* h, hipStream_t s) 
     hipLaunchKernelGGL((apply_bmfma<P, false, true>), grid, block, 0, s, b);
   else
     hipLaunchKernelGGL((apply_bmfma<P, false, false>), grid, block, 0, s, b);
-  return hip_check_b(hipGetLastError(), "apply (band MFMA) launch");
-}
-
-// Tile shape per order: ~64 columns (TYE = 64/P element positions) so a wave spans one tile line;
-// TXE element columns for ~512-node tiles; rows of an element split over NS threads.
-template <int P>
-struct BandShape {
-  static constexpr int TYE = (64 / P) > 0 ? 64 / P : 1;
-  static constexpr int TXE = (8 / P) > 4 ? 4 : ((8 / P) > 0 ? 8 / P : 1);
-  static constexpr int NS = P >= 2 ? 2 : 1;
-};
-
-template <int P>
-static int launch_band_auto(const ApplyArgs& args, const sem_handle* h, hipStream_t s) {
-  using S = BandShape<P>;
-  // coefficient mode: DPP-broadcast lists from ~1M DOFs up (the issue-bound regime), fp64 immediates below (the
-  // launch-latency-bound meshes, whose extra coefficient loads sit on the critical path: profiles/r01/band/dpp_ab.txt);
-  // SEM_BAND_TILE = 3 / 4 forces DPP / immediates (the bitwise-variant tests)
-  const int force = tune(SEM_TUNE_BAND_TILE);
-  const bool dpp = force == 3 || (force != 4 && args.n_local32 >= (1 << 20));
-  if (dpp) return launch_band<P, S::TXE, S::TYE, S::NS, 1>(args, h, s);
-  return launch_band<P, S::TXE, S::TYE, S::NS, 0>(args, h, s);
-}
-
-std::string band_kernel_name(int P, long long n_local) {
-  const int TYE = std::max(1, 64 / P), TXE = std::min(4, std::max(1, 8 / P));
-  const int NS = P >= 2 ? 2 : 1;
-  const int force = tune(SEM_TUNE_BAND_TILE);
-  const bool dpp = force == 3 || (force != 4 && n_local >= (1 << 20));
-  const bool kp = tune(SEM_TUNE_BAND_KP) >= 0;
-  return std::string(kp ? "sem::apply_band_kp<" : "sem::apply_band<") + std::to_string(P) + ", " + std::to_string(TXE) +
-         ", " + std::to_string(TYE) + ", " + std::to_string(NS) + (dpp ? ", dpp" : "") + ">";
+  return hip_check(hipGetLastError(), "apply (band MFMA) launch");
 }
 
 int launch_apply_bmfma(const ApplyArgs& a, const sem_handle* h, hipStream_t s) {
-  switch (h->P) {
-#define SEM_BMCASE(PP) \
-  case PP:             \
-    return launch_bmfma<PP>(a, h, s);
-    SEM_BMCASE(1) SEM_BMCASE(2) SEM_BMCASE(3) SEM_BMCASE(4) SEM_BMCASE(5) SEM_BMCASE(6) SEM_BMCASE(7) SEM_BMCASE(8)
-    SEM_BMCASE(9) SEM_BMCASE(10) SEM_BMCASE(11) SEM_BMCASE(12) SEM_BMCASE(13) SEM_BMCASE(14) SEM_BMCASE(15)
-    SEM_BMCASE(16)
-#undef SEM_BMCASE
-    default:
-      return set_error(SEM_EUNSUPPORTED, "polynomial order outside compiled range");
-  }
+  return dispatch_order(h->P, [&](auto P) { return launch_bmfma<decltype(P)::value>(a, h, s); });
 }
 
-std::string bmfma_kernel_name(int P) {
-  const int TXE = std::max(1, 16 / P);
-  return "sem::apply_bmfma<" + std::to_string(P) + ", " + std::to_string(TXE * P) + " x " +
-         std::to_string(4 * TXE * P) + ">";
-}
-
+// Tile shape (BandShape<P>) and coefficient mode (band_dpp) per order and mesh size: apply_select.h.
 int launch_apply_band(const ApplyArgs& a, const sem_handle* h, hipStream_t s) {
-  switch (h->P) {
-#define SEM_BCASE(PP) \
-  case PP:            \
-    return launch_band_auto<PP>(a, h, s);
-    SEM_BCASE(1) SEM_BCASE(2) SEM_BCASE(3) SEM_BCASE(4) SEM_BCASE(5) SEM_BCASE(6) SEM_BCASE(7) SEM_BCASE(8)
-    SEM_BCASE(9) SEM_BCASE(10) SEM_BCASE(11) SEM_BCASE(12) SEM_BCASE(13) SEM_BCASE(14) SEM_BCASE(15) SEM_BCASE(16)
-#undef SEM_BCASE
-    default:
-      return set_error(SEM_EUNSUPPORTED, "polynomial order outside compiled range");
-  }
+  const bool dpp = band_dpp(tune(SEM_TUNE_BAND_TILE), a.n_local32);
+  return dispatch_order(h->P, [&](auto PC) {
+    constexpr int P = decltype(PC)::value;
+    using S = BandShape<P>;
+    if (dpp) return launch_band<P, S::TXE, S::TYE, S::NS, 1>(a, h, s);
+    return launch_band<P, S::TXE, S::TYE, S::NS, 0>(a, h, s);
+  });
 }
 
 }  // namespace sem

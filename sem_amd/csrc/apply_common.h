@@ -1,4 +1,5 @@
-// Shared device-side definitions of the apply kernels (sem_ops.hip, apply_band.hip).
+// Shared definitions of the apply kernels (apply_tp.hip, apply_band.hip, apply_transpose.hip): the argument
+// struct, the launchers sem_ops.hip calls, and the device-side contraction and buffer helpers.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,6 +8,7 @@
 #include <utility>
 
 #include "gll_consts.h"
+#include "hip_util.h"
 #include "sem_internal.h"
 
 namespace sem {
@@ -30,12 +32,19 @@ struct ApplyArgs {
   int tiles_x, tiles_y, dir_mode;
   unsigned sides;
   int has_e1, has_e2;
-  int n_local32;  // local vector length (MFMA path: < 2^31)
+  int n_local32;  // local vector length, clamped to 2^31 - 1 (the buffer-offset kernels run below 2^28)
   int pos0, pos1; // element-position range (band kernel; pos1 == 0: all positions)
   int diag;       // ablation bits for performance diagnosis (SEM_DIAG env); 0 in production
   unsigned long long* stamps;  // SEM_DIAG bit 8: per-wave s_memtime phase stamps (diagnostic builds only)
 };
 
+// One launcher per kernel kind (apply_select.h picks the kind); each dispatches on h->P.
+int launch_apply_band(const ApplyArgs& a, const sem_handle* h, hipStream_t s);       // apply_band.hip
+int launch_apply_bmfma(const ApplyArgs& a, const sem_handle* h, hipStream_t s);      // apply_band.hip
+int launch_apply_emfma(const ApplyArgs& a, const sem_handle* h, hipStream_t s);      // apply_tp.hip
+int launch_apply_col(const ApplyArgs& a, const sem_handle* h, hipStream_t s);        // apply_tp.hip
+int launch_apply_valu(const ApplyArgs& a, const sem_handle* h, hipStream_t s);       // apply_tp.hip
+int launch_apply_transpose(const ApplyArgs& a, const sem_handle* h, hipStream_t s);  // apply_transpose.hip
 
 // Sum of GLL weights of the elements in [e_lo, e_hi) that hold 1-D node g.
 __device__ __forceinline__ double weight_sum(int64_t g, int P, int e_lo, int e_hi, const double* w) {

@@ -25,18 +25,16 @@
 // reproducible.  Whole-mesh handles only.
 #include <hip/hip_runtime.h>
 
-#include <string>
-
 #include "apply_common.h"
+#include "apply_select.h"
 
 namespace sem {
 
 template <int P>
 struct TCfg {
   static constexpr int n = P + 1;
-  static constexpr int TYE = (64 / P) > 0 ? 64 / P : 1;
-  static constexpr int TXE = (8 / P) > 4 ? 4 : ((8 / P) > 0 ? 8 / P : 1);
-  static constexpr int NS = P >= 2 ? 2 : 1;              // row splits of an element
+  static constexpr int TYE = BandShape<P>::TYE, TXE = BandShape<P>::TXE;  // the band kernel's tile
+  static constexpr int NS = BandShape<P>::NS;            // row splits of an element
   static constexpr int BX = TXE * P, BY = TYE * P;       // lines / columns of the tile
   static constexpr int XW = (BY + 63) / 64;
   static constexpr int LW = 64 * XW;                     // lanes per tile line (X role, epilogue)
@@ -309,7 +307,7 @@ __global__ __launch_bounds__((TCfg<P>::THREADS)) void apply_transpose(const TArg
     }
     zz[e] = val;
   }
-  if (a.cpol == 3) {  // system-scope stores on a mesh whose working set stays in the MALL (band_cpol)
+  if (a.cpol == 3) {  // system-scope stores on a mesh whose working set stays in the MALL (transpose_cpol)
 #pragma unroll
     for (int e = 0; e < C::NE; ++e)
       if (eoff[e] >= 0) bstore_c<17>(ry, eoff[e] * 8, zz[e]);
@@ -349,27 +347,14 @@ static int launch_transpose(const ApplyArgs& g, const sem_handle* h, hipStream_t
   t.nblk = static_cast<int>(nblk);
   t.nbytes = g.n_local32 * 8;
   t.dir_mode = g.dir_mode;
-  t.cpol = 32LL * g.n_local32 < (128LL << 20) ? 3 : 0;
+  t.cpol = transpose_cpol(g.n_local32);
   t.sides = g.sides;
   hipLaunchKernelGGL((apply_transpose<P>), dim3(static_cast<unsigned>(nblk)), dim3(C::THREADS), 0, s, t);
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return SEM_OK;
-  return set_error(SEM_EHIP, std::string("apply (transpose) launch: ") + hipGetErrorString(e));
+  return hip_check(hipGetLastError(), "apply (transpose) launch");
 }
 
-std::string transpose_kernel_name(int P) { return "sem::apply_transpose<" + std::to_string(P) + ">"; }
-
 int launch_apply_transpose(const ApplyArgs& a, const sem_handle* h, hipStream_t s) {
-  switch (h->P) {
-#define SEM_TCASE(PP) \
-  case PP:            \
-    return launch_transpose<PP>(a, h, s);
-    SEM_TCASE(1) SEM_TCASE(2) SEM_TCASE(3) SEM_TCASE(4) SEM_TCASE(5) SEM_TCASE(6) SEM_TCASE(7) SEM_TCASE(8)
-    SEM_TCASE(9) SEM_TCASE(10) SEM_TCASE(11) SEM_TCASE(12) SEM_TCASE(13) SEM_TCASE(14) SEM_TCASE(15) SEM_TCASE(16)
-#undef SEM_TCASE
-    default:
-      return set_error(SEM_EUNSUPPORTED, "polynomial order outside compiled range");
-  }
+  return dispatch_order(h->P, [&](auto P) { return launch_transpose<decltype(P)::value>(a, h, s); });
 }
 
 }  // namespace sem

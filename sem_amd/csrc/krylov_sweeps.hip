@@ -13,6 +13,7 @@
 
 #include <string>
 
+#include "hip_util.h"
 #include "sem_internal.h"
 
 namespace sem {
@@ -125,11 +126,6 @@ __global__ __launch_bounds__(kUpdThreads) void basis_update_kernel(const double*
   if (i < n) w[i] = w[i] - (s0 + s1);
 }
 
-static int hip_check_k(hipError_t e, const char* what) {
-  if (e == hipSuccess) return SEM_OK;
-  return set_error(SEM_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
 }  // namespace sem
 
 extern "C" {
@@ -153,7 +149,7 @@ int sem_basis_dot2(const double* V, int64_t ldv, int k, int64_t n, const double*
   hipLaunchKernelGGL(sem::basis_dot2_kernel<true>, dim3(nch, groups), dim3(sem::kDotThreads), 0, s, V, ldv, k, n, nch,
                      a, b, work);
   hipLaunchKernelGGL(sem::basis_dot2_finish, dim3((2 * k + 255) / 256), dim3(256), 0, s, work, k, nch, out);
-  return sem::hip_check_k(hipGetLastError(), "basis_dot2 launch");
+  return sem::hip_check(hipGetLastError(), "basis_dot2 launch");
 }
 
 int sem_basis_update(const double* V, int64_t ldv, int k, int64_t n, const double* c, double* w, void* stream) {
@@ -166,7 +162,7 @@ int sem_basis_update(const double* V, int64_t ldv, int k, int64_t n, const doubl
   // plain loads in the update pass (non-temporal measured slower there, round 5)
   hipLaunchKernelGGL(sem::basis_update_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(sem::kUpdThreads), 0, s,
                      V, ldv, k, n, c, w);
-  return sem::hip_check_k(hipGetLastError(), "basis_update launch");
+  return sem::hip_check(hipGetLastError(), "basis_update launch");
 }
 
 }  // extern "C"

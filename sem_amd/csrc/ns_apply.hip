@@ -729,11 +729,6 @@ static void launch_ns_tile(const NsArgs& a, hipStream_t s) {
                      ntiles, per_xcd);
 }
 
-static int hip_check_ns(hipError_t e, const char* what) {
-  if (e == hipSuccess) return SEM_OK;
-  return set_error(SEM_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
 }  // namespace sem
 
 extern "C" {
@@ -800,27 +795,19 @@ int sem_ns_apply(sem_handle* h, const sem_ns_desc* d, const double* u, const dou
   // the band form by default; the tile form on request (SEM_NS_APPLY=1, in-process A/B: results agree to
   // rounding, not bitwise) and for strips beyond the band form's 32-bit buffer offsets
   const bool tile = sem::tune(SEM_TUNE_NS_APPLY) == 1;
-  switch (h->P) {
-#define SEM_NSCASE(PP)                                                                              \
-  case PP:                                                                                          \
-    if (form == (sem::NS_P | sem::NS_UV_OUT)) {                                                     \
-      if (tile || !sem::launch_ns_band<PP, sem::NS_P | sem::NS_UV_OUT>(a, s))                       \
-        sem::launch_ns_tile<PP, sem::NS_P | sem::NS_UV_OUT>(a, s);                                  \
-    } else if (form == (sem::NS_U | sem::NS_P | sem::NS_C_OUT)) {                                   \
-      if (tile || !sem::launch_ns_band<PP, sem::NS_U | sem::NS_P | sem::NS_C_OUT>(a, s))            \
-        sem::launch_ns_tile<PP, sem::NS_U | sem::NS_P | sem::NS_C_OUT>(a, s);                       \
-    } else {                                                                                        \
-      if (tile || !sem::launch_ns_band<PP, sem::NS_ALL>(a, s)) sem::launch_ns_tile<PP, sem::NS_ALL>(a, s); \
-    }                                                                                               \
-    break;
-    SEM_NSCASE(1) SEM_NSCASE(2) SEM_NSCASE(3) SEM_NSCASE(4) SEM_NSCASE(5) SEM_NSCASE(6) SEM_NSCASE(7) SEM_NSCASE(8)
-    SEM_NSCASE(9) SEM_NSCASE(10) SEM_NSCASE(11) SEM_NSCASE(12) SEM_NSCASE(13) SEM_NSCASE(14) SEM_NSCASE(15)
-    SEM_NSCASE(16)
-#undef SEM_NSCASE
-    default:
-      return sem::set_error(SEM_EUNSUPPORTED, "polynomial order outside compiled range");
-  }
-  return sem::hip_check_ns(hipGetLastError(), "ns apply launch");
+  const auto launch = [&](auto PC, auto FC) {
+    constexpr int P = decltype(PC)::value, F = decltype(FC)::value;
+    if (tile || !sem::launch_ns_band<P, F>(a, s)) sem::launch_ns_tile<P, F>(a, s);
+    return SEM_OK;
+  };
+  constexpr int kGrad = sem::NS_P | sem::NS_UV_OUT, kDiv = sem::NS_U | sem::NS_P | sem::NS_C_OUT;
+  const int st = sem::dispatch_order(h->P, [&](auto PC) {
+    if (form == kGrad) return launch(PC, std::integral_constant<int, kGrad>{});
+    if (form == kDiv) return launch(PC, std::integral_constant<int, kDiv>{});
+    return launch(PC, std::integral_constant<int, sem::NS_ALL>{});
+  });
+  if (st) return st;
+  return sem::hip_check(hipGetLastError(), "ns apply launch");
 }
 
 }  // extern "C"

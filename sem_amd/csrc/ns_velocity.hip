@@ -32,6 +32,7 @@
 
 #include <string>
 
+#include "hip_util.h"
 #include "sem_internal.h"
 
 namespace sem {
@@ -282,11 +283,6 @@ __global__ __launch_bounds__(256) void velocity_blocks_kernel(const VelocityArgs
   }
 }
 
-static int hip_check_v(hipError_t e, const char* what) {
-  if (e == hipSuccess) return SEM_OK;
-  return set_error(SEM_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
 }  // namespace sem
 
 extern "C" {
@@ -347,14 +343,14 @@ static int velocity_blocks_impl(sem_handle* h, const sem_velocity_desc* d, doubl
     int64_t cs[6];
     sem_condensed_block_sizes(h, nc, cs);
     for (int i = 0; i < 6; ++i)
-      if ((st = sem::hip_check_v(hipMemsetAsync(cond[i], 0, cs[i] * (c1 - c0) * sizeof(double), s), "memset blocks")))
+      if ((st = sem::hip_check(hipMemsetAsync(cond[i], 0, cs[i] * (c1 - c0) * sizeof(double), s), "memset blocks")))
         return st;
   } else {
     const int64_t szA = sz[0] / (h->ex_end - h->ex_begin) * (c1 - c0);
-    if (h->P > 1 && (st = sem::hip_check_v(hipMemsetAsync(AII, 0, szA * sizeof(double), s), "memset A_II")))
+    if (h->P > 1 && (st = sem::hip_check(hipMemsetAsync(AII, 0, szA * sizeof(double), s), "memset A_II")))
       return st;
   }
-  if ((st = sem::hip_check_v(hipMemsetAsync(D, 0, sz[1] * sizeof(double), s), "memset D"))) return st;
+  if ((st = sem::hip_check(hipMemsetAsync(D, 0, sz[1] * sizeof(double), s), "memset D"))) return st;
   sem::VelocityArgs a{};
   a.tab = h->d_tab;
   a.cu = d->cu;
@@ -399,7 +395,7 @@ static int velocity_blocks_impl(sem_handle* h, const sem_velocity_desc* d, doubl
   }
   const int64_t rows = (h->line_end - h->line_begin + 1) * nc * h->NY;
   hipLaunchKernelGGL(sem::velocity_blocks_kernel, dim3(static_cast<unsigned>((rows + 255) / 256)), dim3(256), 0, s, a);
-  return sem::hip_check_v(hipGetLastError(), "velocity blocks launch");
+  return sem::hip_check(hipGetLastError(), "velocity blocks launch");
 }
 
 int sem_velocity_blocks(sem_handle* h, const sem_velocity_desc* d, double* AII, double* D, double* aIB, double* aBI,

@@ -330,6 +330,45 @@ def test_bad_arguments_raise(gpu):
         mesh.apply(x.float(), c_stiff=1.0)
 
 
+def test_kernel_names(gpu, tuning):
+    """sem_kernel_name reports the kernel sem_apply selects (sem_amd/csrc/apply_select.h): tile shapes per order,
+    the knobs' variants, and the DPP coefficient mode from 2^20 local nodes up (the two P = 8 meshes straddle it).
+    Handles only; nothing is launched."""
+    from sem_amd import _lib
+    from sem_amd.device import get_mesh
+    A = _lib
+    m4 = get_mesh(4, 3, 2, 0.1, 0.1)
+    assert m4.kernel_name() == m4.kernel_name(A.ALGO_BAND) == "sem::apply_band_kp<4, 2, 16, 2>"
+    assert m4.kernel_name(A.ALGO_COLUMN) == "sem::apply_tp_col<4, 2, 64, 1>"
+    assert m4.kernel_name(A.ALGO_MFMA) == "sem::apply_bmfma<4, 16 x 64>"
+    assert m4.kernel_name(A.ALGO_VALU) == "sem::apply_tp_valu<4>"
+    tuning(A.TUNE_BAND_TILE, 3)
+    assert m4.kernel_name(A.ALGO_BAND) == "sem::apply_band_kp<4, 2, 16, 2, dpp>"
+    tuning(A.TUNE_BAND_TILE, 0)
+    tuning(A.TUNE_BAND_KP, -1)
+    assert m4.kernel_name(A.ALGO_BAND) == "sem::apply_band<4, 2, 16, 2>"
+    tuning(A.TUNE_BAND_KP, 0)
+    m1 = get_mesh(1, 2, 2, 0.1, 0.1)
+    assert m1.kernel_name() == "sem::apply_band_kp<1, 4, 64, 1>"
+    assert m1.kernel_name(A.ALGO_MFMA) == "sem::apply_bmfma<1, 16 x 64>"
+    m16 = get_mesh(16, 1, 1, 0.1, 0.1)
+    assert m16.kernel_name() == "sem::apply_band_kp<16, 1, 4, 2>"
+    assert m16.kernel_name(A.ALGO_MFMA) == "sem::apply_bmfma<16, 16 x 64>"
+    lo, hi = get_mesh(8, 127, 128, 0.1, 0.1), get_mesh(8, 128, 128, 0.1, 0.1)
+    assert lo.n_local == 1042425 < 2 ** 20 <= hi.n_local == 1050625
+    assert lo.kernel_name() == "sem::apply_band_kp<8, 1, 8, 2>"
+    assert hi.kernel_name() == "sem::apply_band_kp<8, 1, 8, 2, dpp>"
+    with pytest.raises(ValueError, match="algo"):
+        m4.kernel_name(5)
+    tuning(A.TUNE_MFMA_TILE, 3)   # the element-block MFMA kernel: small / persistent large tiles, P <= 15
+    assert m4.kernel_name(A.ALGO_MFMA) == "sem::apply_tp_mfma<4, 4, 4, 4, false, true>"
+    assert hi.kernel_name(A.ALGO_MFMA) == "sem::apply_tp_mfma<8, 4, 4, 4, true, false>"
+    assert lo.kernel_name(A.ALGO_MFMA) == "sem::apply_tp_mfma<8, 4, 4, 4, true, false>"
+    assert get_mesh(8, 64, 64, 0.1, 0.1).kernel_name(A.ALGO_MFMA) == "sem::apply_tp_mfma<8, 2, 2, 4, false, true>"
+    with pytest.raises(RuntimeError, match="P <= 15"):
+        m16.kernel_name(A.ALGO_MFMA)
+
+
 @pytest.mark.parametrize("P,nex,ney,eb,ee", [(8, 64, 64, 0, 64), (8, 40, 13, 10, 30), (4, 9, 7, 2, 9), (12, 5, 3, 0, 5),
                                              (6, 7, 5, 3, 4), (8, 1024, 8, 0, 1024)])
 @pytest.mark.parametrize("full", [False, True])
