@@ -735,8 +735,6 @@ class NestedDissectionSolver(VelocityJacobianSolver):
             R = dims[:, 0]
             if form == 1:
                 lanes, rows = 1, 256
-            elif form == 2:
-                lanes, rows = 64, 8
             else:
                 lanes, rows = self._launch_shape(dims[:, 1], R)
             nt = (R + rows - 1) // rows

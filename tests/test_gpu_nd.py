@@ -1,7 +1,10 @@
 """GPU tests of the nested-dissection velocity solve (sem_amd/solvers/nested_dissection.py, HIP steps
-sem_front_gemv / sem_front_scatter): the solve of the oracle's Dirichlet-row-replaced velocity Jacobian
-(NavierStokes_Solver.py:176-192) against SciPy's sparse solve of the same matrix, bitwise graph replay against the
-eager solve, agreement with the torch path of the same factors, and the factor's backward-error probe."""
+sem_front_gemv / sem_leaf_forward / sem_front_sparse_rows / sem_front_scatter): the solve of the oracle's
+Dirichlet-row-replaced velocity Jacobian (NavierStokes_Solver.py:176-192) against SciPy's sparse solve of the same
+matrix, bitwise graph replay against the eager solve, agreement with the torch path of the same factors, and the
+factor's backward-error probe.  The kernels themselves are tested one launch at a time, at every launch shape, in
+test_gpu_front_kernels.py; here the planner's tables (tiles, offsets, the scatter after each level) are what the
+whole solve checks, the two mid-size meshes of test_nd_solve_wide_tiles for the wide tiles."""
 import numpy as np
 import pytest
 import scipy.sparse.linalg as spla
@@ -32,8 +35,7 @@ def _kw(ns, u, v, Re, dev):
                 jvv=t(Re * (ns.Gy @ v)), juv=t(Re * (ns.Gy @ u)), jvu=t(Re * (ns.Gx @ v)))
 
 
-@pytest.mark.parametrize("P,nex,ney,Re", CASES)
-def test_nd_solve_matches_sparse_lu(P, nex, ney, Re):
+def _solve_matches_sparse_lu(P, nex, ney, Re):
     from sem_amd.solvers.nested_dissection import NestedDissectionSolver
     dev = torch.device("cuda", 0)
     ns, u, v = oracle_velocity_jacobian(P, nex, ney, Re, seed=P * 10 + nex)
@@ -52,7 +54,7 @@ def test_nd_solve_matches_sparse_lu(P, nex, ney, Re):
     eta = np.abs(res).max() / (abs(J).sum(axis=1).max() * np.abs(got).max() + max(np.abs(bu).max(), np.abs(bv).max()))
     assert eta <= (1e-15 if vs.refine else 1e-13), (eta0, eta)
     if vs.refine:    # the refinement step's operator here is SciPy's (host): not capturable
-        return
+        return vs
     # graph replay is the eager solve, bit for bit
     B = torch.stack((torch.as_tensor(bu, device=dev).view(vs.NX, -1), torch.as_tensor(bv, device=dev).view(vs.NX, -1)),
                     1).reshape(vs.NX, -1)
@@ -61,6 +63,29 @@ def test_nd_solve_matches_sparse_lu(P, nex, ney, Re):
     gu, gv = vs.solve(torch.as_tensor(bu, device=dev), torch.as_tensor(bv, device=dev))
     assert torch.equal(gu, xe.view(vs.NX, 2, -1)[:, 0].reshape(-1))
     assert torch.equal(gv, xe.view(vs.NX, 2, -1)[:, 1].reshape(-1))
+    return vs
+
+
+@pytest.mark.parametrize("P,nex,ney,Re", CASES)
+def test_nd_solve_matches_sparse_lu(P, nex, ney, Re):
+    _solve_matches_sparse_lu(P, nex, ney, Re)
+
+
+# (mesh, the (back, lanes, rows) launches it is here for): the planner takes the wide tile of a lane count only
+# from 256 wide-tile workgroups in a level on (_launch_shape), which the small meshes above never reach
+WIDE_CASES = [((2, 40, 40, 100.0), {(1, 4, 128), (1, 8, 64)}),
+              ((8, 12, 12, 100.0), {(0, 16, 32), (1, 16, 32)})]
+
+
+@pytest.mark.parametrize("case,shapes", WIDE_CASES, ids=["P2-40x40", "P8-12x12"])
+def test_nd_solve_wide_tiles(case, shapes):
+    """The same solve-against-SciPy checks on two mid-size meshes (N = 6561 and 9409) whose plans hold wide-tile
+    launches: their tiles, output offsets and the scatter after them.  If the planner's rule changes and a shape
+    below leaves the plan, pick meshes that bring it back."""
+    from sem_amd import _lib
+    vs = _solve_matches_sparse_lu(*case)
+    planned = {(d.back, d.lanes, d.rows) for d, *_ in vs._hip if isinstance(d, _lib.SemFrontLaunch) and d.form == 0}
+    assert shapes <= planned, (sorted(shapes - planned), sorted(planned))
 
 
 def test_nd_hip_steps_match_the_torch_path():
