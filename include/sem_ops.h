@@ -513,9 +513,11 @@ int sem_dense_inverse_small(const double* A, int64_t lda, double* X, int64_t ldx
  * rows when pin_first (the residual's statement order, :116-120) and after them otherwise (:159-160).
  * u, v, p, T, cu, cv, j**, dval_* are nullable (NULL = zeros; cu, cv: ones); a NULL output is not
  * computed.  u, v, ru, rv hold node (gx, gy) at gx * uv_pitch + gy (0 = NY: plain vectors; 2 NY: the
- * line-interleaved [u | v] layout of the velocity solve).  `pin` is a global node index.  On an
- * element-column strip handle (ABI 5) every vector holds the strip's lines; the two interface lines
- * get partial sums over the strip's elements, and pointwise terms, Dirichlet rows and the pinned row of
+ * line-interleaved [u | v] layout of the velocity solve).  cu, cv and every other operand are plain vectors
+ * (node at (gx - line_begin) NY + gy): cu may be u itself and cv may be v itself only when u, v are plain
+ * vectors too (uv_pitch 0 or NY); cu == u or cv == v with another pitch is SEM_EINVAL.  `pin` is a global
+ * node index.  On an element-column strip handle (ABI 5) every vector holds the strip's lines; the two
+ * interface lines get partial sums over the strip's elements, and pointwise terms, Dirichlet rows and the pinned row of
  * the right interface line are written by its right-hand owner only (0 here), so summing the interface
  * lines across strips (sem_interface_pack/unpack + an all-reduce) gives the whole-mesh rows. */
 typedef struct sem_ns_desc {

@@ -738,6 +738,12 @@ int sem_ns_apply(sem_handle* h, const sem_ns_desc* d, const double* u, const dou
   if (!h || !d) return sem::set_error(SEM_EINVAL, "null argument");
   if (d->uv_pitch != 0 && d->uv_pitch < h->NY) return sem::set_error(SEM_EINVAL, "uv_pitch below the line length");
   if (d->pin < -1 || d->pin >= h->NX * h->NY) return sem::set_error(SEM_EINVAL, "pinned node out of range");
+  // cu, cv are plain vectors: a cu that is u itself (cv: v) is read through u's layout by the band form and
+  // through the plain index by the tile form, the same node only when u, v are plain vectors too
+  if (d->uv_pitch != 0 && d->uv_pitch != h->NY) {
+    if (d->cu && d->cu == u) return sem::set_error(SEM_EINVAL, "cu aliases u, but u is a line view (uv_pitch != NY)");
+    if (d->cv && d->cv == v) return sem::set_error(SEM_EINVAL, "cv aliases v, but v is a line view (uv_pitch != NY)");
+  }
   int cur = -1;
   if (hipGetDevice(&cur) != hipSuccess || cur != h->device)
     return sem::set_error(SEM_EINVAL, "handle belongs to device " + std::to_string(h->device) +

@@ -246,7 +246,8 @@ class Mesh:
                  stream=None):
         """Fused Navier-Stokes residuals (include/sem_ops.h, sem_ns_apply): ru, rv, rc in one launch.
         u, v, ru, rv are plain vectors or (NX, NY) line views sharing one row stride (the velocity
-        solve's interleaved [u | v] lines); a None output is not computed."""
+        solve's interleaved [u | v] lines); a None output is not computed.  Every other operand is a plain
+        vector: cu may be u itself (cv: v) only when u, v are plain vectors too (ValueError otherwise)."""
         pitch = set()
         views = []
         for nm, t in (("u", u), ("v", v), ("ru", ru), ("rv", rv)):
