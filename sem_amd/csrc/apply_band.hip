@@ -26,7 +26,12 @@
 // *ghost* element past the last one: tiles run over ncols+1 x ney+1 element positions, and a
 // ghost element contributes only its row / column 0 (left element only).  Every node therefore
 // goes through the same wave-uniform fast path, and the ghost tiles are light.
-// Barriers: staged tile in LDS -> X and Y contractions run concurrently -> X epilogue.
+// Barriers: staged tile in LDS -> X and Y contractions run concurrently -> epilogue (every wave).
+// One workgroup's dependent chain is what a launch-latency-bound mesh pays in full (all tiles are resident in one
+// round and run in step), so nothing waits on memory between the barriers: the staged window's loads are waited
+// for before barrier 1, the pointwise u, v loads issued there are first waited for in the epilogue, every kernel
+// argument is in SGPRs before barrier 1 (no scalar load behind it), and the epilogue issues the LDS reads of all
+// its nodes in one batch.  tools/isa_budget.py --chain reports all three from the assembly.
 #include <hip/hip_runtime.h>
 
 #include "apply_common.h"
@@ -363,26 +368,28 @@ __device__ __forceinline__ NodeOps load_node_ops(const BandArgs& a, int p) {
   return o;
 }
 
-// Operator value z of one node -> + extra / accumulate terms, Dirichlet rows (no memory access).
+// Operator value z of one node -> + extra / accumulate terms, Dirichlet rows (no memory access).  NY and ex_end
+// come from the caller's registers (the preloaded arguments of apply_band_kp), not from the struct: read from it
+// here, their scalar loads sank into the epilogue of every tile.
 template <bool FULL>
-__device__ __forceinline__ double finish_node(const BandArgs& a, const NodeOps& o, int gx, int gy, double xv,
-                                              double z) {
+__device__ __forceinline__ double finish_node(const BandArgs& a, int NY, int ex_end, const NodeOps& o, int gx, int gy,
+                                              double xv, double z) {
   if constexpr (FULL) {
     // pointwise terms are node values, not partial sums: on a strip's right interface line they
     // are left to the right-hand owner (the exchange sums the two strips' values)
-    const bool own = !(gx == a.lb1 && a.ex_end < a.nex);
+    const bool own = !(gx == a.lb1 && ex_end < a.nex);
     if (a.has_e1 && own) z = fma(a.cE * o.ea, o.eb, z);
     if (a.has_e2 && own) z = fma(a.cE * o.ec, o.ed, z);
     if (a.cA != 0.0 && own) z = fma(a.cA, o.ya, z);
   }
   if (a.dir_mode != SEM_DIR_NONE) {
     const bool side = ((a.sides & SEM_SIDE_W) && gx == 0) || ((a.sides & SEM_SIDE_E) && gx == a.NXg - 1) ||
-                      ((a.sides & SEM_SIDE_S) && gy == 0) || ((a.sides & SEM_SIDE_N) && gy == a.NY - 1);
+                      ((a.sides & SEM_SIDE_S) && gy == 0) || ((a.sides & SEM_SIDE_N) && gy == NY - 1);
     bool isd = side;
     if constexpr (FULL) isd = a.mask ? (o.mk & 0xff) != 0 : side;
     if (isd) {
       // an interface line's Dirichlet row is written by its owner (the right strip) only
-      const bool owner = !(gx == a.lb1 && a.ex_end < a.nex);
+      const bool owner = !(gx == a.lb1 && ex_end < a.nex);
       const double dv = FULL ? o.dv : 0.0;
       if (!owner)
         z = 0.0;
@@ -449,7 +456,7 @@ __device__ __forceinline__ void band_body(const double* __restrict__ px, const d
   using CL = CList<P, NS>;
   constexpr bool DPP = CM == 1;
   constexpr int n = C::n, BX = C::BX, PT = C::PT, PY = C::PY, LW = C::LW, NW = C::NW;
-  __shared__ double Ts[C::RX * PT];
+  __shared__ double Ts[C::RX * PT + 1];   // + the dump slot of the extra-column staging step (never read)
   __shared__ double XK[BX * PY];
   // XG, YG are allocated for the Laplacian-only form (GRAD = false) too although it never touches them: the
   // smaller footprint let 8 workgroups share a CU instead of 6 and ran 3 % slower at 1024^2 (round-6 A/B,
@@ -522,7 +529,7 @@ __device__ __forceinline__ void band_body(const double* __restrict__ px, const d
     const int gy = gy0 - P + cc;
     const bool ok = k < C::NSL && rr < C::RX;
     const unsigned vx = (ok && gy >= 0 && gy < NY) ? static_cast<unsigned>(gy) * 8u : 0x80000000u;
-    xts[j] = ok ? rr * PT + cc : -1;
+    xts[j] = ok ? rr * PT + cc : C::RX * PT;  // a lane without a node writes the dump slot
     sX[j] = bload(rx, static_cast<int>(vx + static_cast<unsigned>(line0 + k * lstep)));
   }
   // epilogue nodes of this thread: q = tid + e*THREADS -> tile line r = q / LW, column c = q % LW
@@ -551,6 +558,13 @@ __device__ __forceinline__ void band_body(const double* __restrict__ px, const d
     BPIN(a.lb1);
     BPIN(a.nex);
   }
+  if constexpr (FULL) {  // both kernels: the epilogue-only fields of the optional terms
+    BPIN(a.cE);
+    BPIN(a.cA);
+    BPIN(a.has_e1);
+    BPIN(a.has_e2);
+    BPIN(a.mask);
+  }
 
   // ---- LDS: staged window, weights
 #pragma unroll
@@ -558,10 +572,15 @@ __device__ __forceinline__ void band_body(const double* __restrict__ px, const d
     if (k < C::NSL - 1 || w + NW * k < C::RX) Ts[(w + NW * k) * PT + lane] = sA[k];
 #pragma unroll
   for (int j = 0; j < C::NXL; ++j)
-    if (xts[j] >= 0) Ts[xts[j]] = sX[j];
+    Ts[xts[j]] = sX[j];
   if (tid < n) ws[tid] = wsv;
   // the epilogue's pointwise operands: issued after the staged window has gone to LDS, so they land during the
-  // contractions (round 4)
+  // contractions (round 4).  They do only while nothing between here and the epilogue makes the compiler wait for
+  // an older load: vmcnt retires in order, so such a wait drains these too.  The staging writes above are
+  // therefore unconditional (a predicated write left sX's wait inside a skippable branch and cost every role
+  // path an s_waitcnt vmcnt(0) before its first window read); the role paths now carry no vmcnt wait and the
+  // epilogue waits vmcnt(2 NE - 1 ..  0) as it consumes u, v (tools/isa_budget.py --chain,
+  // tests/test_band_chain_isa.py)
   if (nt_uv) {
 #pragma unroll
     for (int e = 0; e < C::NE; ++e) {
@@ -667,13 +686,33 @@ __device__ __forceinline__ void band_body(const double* __restrict__ px, const d
     special = special || ((sd & SEM_SIDE_W) && gx0 == 0) || ((sd & SEM_SIDE_E) && gxl >= NXg - 1) ||
               ((sd & SEM_SIDE_S) && gy0 == 0) || ((sd & SEM_SIDE_N) && gyl >= NY - 1);
   }
-  double zz[C::NE];
+  // the LDS reads of all NE nodes are issued before the first use, so a thread pays one LDS round trip (two in a
+  // special tile) instead of two per node; the per-node arithmetic below keeps its order
+  double rxk[C::NE], ryk[C::NE], rxg[C::NE], ryg[C::NE], rxv[C::NE] = {};
 #pragma unroll
   for (int e = 0; e < C::NE; ++e) {
     const int q = tid + e * C::THREADS;
     const int r = q / LW, c = q - r * LW;
     const int o = r * PY + c;
-    double z = XK[o] + YK[o];
+    rxk[e] = XK[o];
+    ryk[e] = YK[o];
+    rxg[e] = GRAD ? XG[o] : 0.0;
+    ryg[e] = GRAD ? YG[o] : 0.0;
+  }
+  if (special) {
+#pragma unroll
+    for (int e = 0; e < C::NE; ++e) {
+      const int q = tid + e * C::THREADS;
+      const int r = q / LW, c = q - r * LW;
+      rxv[e] = Ts[(P + r) * PT + P + c];
+    }
+  }
+  double zz[C::NE];
+#pragma unroll
+  for (int e = 0; e < C::NE; ++e) {
+    const int q = tid + e * C::THREADS;
+    const int r = q / LW, c = q - r * LW;
+    double z = rxk[e] + ryk[e];
     if (a.fM != 0.0) {   // the mass term (not on the CD / NS hot paths: a uniform branch, its weights from LDS)
       const int i = r % P, me = m0 + r / P, j = c % P, ne = n0 + c / P;
       const double mx = i != 0 ? ws[i] : (me - 1 >= pex_begin ? wP : 0.0) + (me < pex_end ? w0 : 0.0);
@@ -681,10 +720,10 @@ __device__ __forceinline__ void band_body(const double* __restrict__ px, const d
       z = fma(a.fM * mx * my, Ts[(P + r) * PT + P + c], z);
     }
     if constexpr (GRAD) {
-      z = fma(has_u ? pu[e] : 1.0, XG[o], z);
-      z = fma(has_v ? pv[e] : 1.0, YG[o], z);
+      z = fma(has_u ? pu[e] : 1.0, rxg[e], z);
+      z = fma(has_v ? pv[e] : 1.0, ryg[e], z);
     }
-    if (special && eoff[e] >= 0) z = finish_node<FULL>(a, ops[e], gx0 + r, gy0 + c, Ts[(P + r) * PT + P + c], z);
+    if (special && eoff[e] >= 0) z = finish_node<FULL>(a, NY, pex_end, ops[e], gx0 + r, gy0 + c, rxv[e], z);
     zz[e] = z;
   }
   if ((a.cpol & 255) == 3) {   // system-scope stores (a mesh whose working set stays in the MALL)
@@ -917,7 +956,7 @@ __global__ __launch_bounds__(BMCfg<P>::THREADS) void apply_bmfma(const BandArgs 
   // columns 64..SC-1 of its lines in NXL more loads; absent columns / lines load 0 through out-of-range offsets
   constexpr int NSL = (C::SL + NW - 1) / NW, SCX = C::SC - 64, NXL = SCX > 0 ? (NSL * SCX + 63) / 64 : 0;
   static_assert(C::SC <= 128, "staged columns");
-  __shared__ double Ts[C::SL * PT];
+  __shared__ double Ts[C::SL * PT + 1];   // + the dump slot of the extra-column staging step (never read)
   __shared__ double ws[P + 1];   // GLL weights: one LDS read per weight instead of a compare-select chain
   // the Ab operands live in LDS, read per k-step (round 6): as per-lane registers they held 2 KS doubles per lane through
   // the whole kernel and, with the accumulators, capped the kernel at 4 waves per SIMD
@@ -936,6 +975,28 @@ __global__ __launch_bounds__(BMCfg<P>::THREADS) void apply_bmfma(const BandArgs 
   const auto rx = brsrc(a.x, nbytes), ry = brsrc(a.y, nbytes);
   const bool has_u = (a.flags & 1) != 0, has_v = (a.flags & 2) != 0;
   const auto ru = brsrc(a.cu, has_u ? nbytes : 0), rv = brsrc(a.cv, has_v ? nbytes : 0);
+  // the epilogue's fields: fetched at kernel entry, not after the products (see BandArgs)
+  const int ex_end = a.ex_end;
+  BPIN(a.fKx);
+  BPIN(a.fKy);
+  BPIN(a.fM);
+  BPIN(a.fX);
+  BPIN(a.fY);
+  BPIN(a.ney);
+  BPIN(a.ex_begin);
+  BPIN(ex_end);
+  BPIN(a.nex);
+  BPIN(a.NXg);
+  BPIN(a.dir_mode);
+  BPIN(a.sides);
+  BPIN(a.cpol);
+  if constexpr (FULL) {
+    BPIN(a.cE);
+    BPIN(a.cA);
+    BPIN(a.has_e1);
+    BPIN(a.has_e2);
+    BPIN(a.mask);
+  }
 
   // ---- tables first (their loads return under the staging loads), then the staged window
   const double wsv = tid <= P ? kGllW<P>.v[tid] : 0.0;
@@ -961,7 +1022,7 @@ __global__ __launch_bounds__(BMCfg<P>::THREADS) void apply_bmfma(const BandArgs 
     const int gy = gy0 - P + cc;
     const bool ok = k < NSL && rr < C::SL;
     const unsigned vx = (ok && gy >= 0 && gy < NY) ? static_cast<unsigned>(gy) * 8u : 0x80000000u;
-    xts[j] = ok ? C::ts(rr, cc) : -1;
+    xts[j] = ok ? C::ts(rr, cc) : C::SL * PT;
     sX[j] = bload(rx, static_cast<int>(vx + static_cast<unsigned>(line0 + k * lstep)));
   }
   // this lane's epilogue nodes: tile row i = lk + 4 r, column gy0 + w CB + lr
@@ -978,7 +1039,7 @@ __global__ __launch_bounds__(BMCfg<P>::THREADS) void apply_bmfma(const BandArgs 
     if (k < NSL - 1 || w + NW * k < C::SL) Ts[C::ts(w + NW * k, lane)] = sA[k];
 #pragma unroll
   for (int j = 0; j < NXL; ++j)
-    if (xts[j] >= 0) Ts[xts[j]] = sX[j];
+    Ts[xts[j]] = sX[j];
   if (tid <= P) ws[tid] = wsv;
 #pragma unroll
   for (int q = 0; q < NAB; ++q) {
@@ -1043,7 +1104,7 @@ __global__ __launch_bounds__(BMCfg<P>::THREADS) void apply_bmfma(const BandArgs 
   const double sxk = a.fKx * my, sxg = a.fX * my;
   // tile-uniform: can a node of this tile lack a neighbour element (strip / domain edge) or be a Dirichlet row?
   const int gxl = gx0 + rows_ok - 1, gyl = gy0 + C::NB * C::CB - 1;
-  const bool xedge = gx0 <= a.ex_begin * P || gxl >= a.ex_end * P, yedge = gy0 == 0 || gyl >= NY - 1;
+  const bool xedge = gx0 <= a.ex_begin * P || gxl >= ex_end * P, yedge = gy0 == 0 || gyl >= NY - 1;
   bool special = FULL;
   if (a.dir_mode != SEM_DIR_NONE) {
     const unsigned sd = a.sides;
@@ -1060,7 +1121,7 @@ __global__ __launch_bounds__(BMCfg<P>::THREADS) void apply_bmfma(const BandArgs 
   for (int r = 0; r < 4; ++r) {
     const int i = lk + 4 * r, gx = gx0 + i;
     const int li = gx % P, me = gx / P;
-    const bool hasLx = li == 0 && me - 1 >= a.ex_begin, hasRx = li != 0 || me < a.ex_end;
+    const bool hasLx = li == 0 && me - 1 >= a.ex_begin, hasRx = li != 0 || me < ex_end;
     const double mx = li != 0 ? ws[li] : (hasLx ? wP : 0.0) + (hasRx ? w0 : 0.0);
     double XK = xk[r], XG = xg[r], YK = yk[r], YG = yg[r];
     double z;
@@ -1078,7 +1139,7 @@ __global__ __launch_bounds__(BMCfg<P>::THREADS) void apply_bmfma(const BandArgs 
         z = fma(has_u ? pu[r] : 1.0, sxg * XG, z);
         z = fma(a.fY * (has_v ? pv[r] : 1.0), mx * YG, z);
       }
-      if (special) z = finish_node<FULL>(a, ops[r], gx, gyn, xv, z);
+      if (special) z = finish_node<FULL>(a, NY, ex_end, ops[r], gx, gyn, xv, z);
     } else {
       z = fma(sxk, XK, a.fKy * mx * YK);
       if constexpr (GRAD) {
