@@ -485,6 +485,68 @@ typedef struct sem_leaf_launch {
 } sem_leaf_launch;
 int sem_leaf_forward(const sem_leaf_launch* d, void* stream);
 
+/* ---- transposed nested-dissection solve J^T x = b (entry points added at ABI 15) ---- */
+/* The steps of NestedDissectionSolver.solve_T: the same stored operators as the forward solve, streamed the other
+ * way (no transposed copies).  What exists: the velocity factor's transposed solve.  What does not: a transposed
+ * Schur solve, strips, a transposed line condensation.
+ * sem_front_gemv_t: one launch = one level of y_f = A_f^T x_f.  Item f has a ROW-MAJOR operator at op[f] (device
+ * address, 16-byte aligned; dims[4 f .. 4 f + 2] = R_f operand rows, K_f output columns, leading dimension ld_f;
+ * K_f and ld_f even, K_f <= ld_f), its R_f operand positions in W at xidx[xoff[f] ..] (-1: a zero operand) and
+ *   back = 0: stage[yoff[f] + c] = (A_f^T x)_c
+ *   back = 1: W[yidx[yoff[f] + c]] -= (A_f^T x)_c   (targets distinct and not operands of the same launch).
+ * tiles[4 b .. 4 b + 2] = (item, first column, part) of workgroup b (tiles[4 b + 3] unused): a workgroup takes
+ * 2 `lanes` columns (lanes = 64, 32, 16, 8 or 4: `lanes` lanes along the contiguous columns, 256 / lanes row groups)
+ * and part p < nparts of the item's rows, rows [p rp, min(R_f, (p + 1) rp)) with rp = ceil(R_f / nparts); every
+ * (column tile, part) of an item must be in the table.  nparts = 1: the workgroup finishes its outputs.
+ * 1 < nparts <= SEM_FRONT_T_MAX_PARTS: the parts' sums go to partials[poff[f] + p K_f + c] (poff: disjoint ranges
+ * of nparts K_f doubles) and a second kernel of the same launch call adds them in increasing p.  kmax >= every R_f
+ * (<= 8192: SEM_EUNSUPPORTED above).  Summation order of an output: each row group's rows increasing, the row
+ * groups increasing, the parts increasing -- no atomics, bitwise repeatable for a given (lanes, nparts).  Nothing is
+ * allocated; all arrays are device memory; stream-ordered and graph-capturable. */
+#define SEM_FRONT_T_MAX_PARTS 16
+typedef struct sem_front_t_launch {
+  int ntiles, lanes, nparts, kmax, back;
+  const int64_t* op;
+  const int32_t* dims;
+  const int64_t* xoff;
+  const int64_t* yoff;
+  const int64_t* poff;
+  const int32_t* tiles;
+  const int32_t* xidx;
+  const int32_t* yidx;
+  double* W;
+  double* stage;
+  double* partials;
+} sem_front_t_launch;
+int sem_front_gemv_t(const sem_front_t_launch* d, void* stream);
+/* A_bi^T x_b on A_bi's sparsity pattern read the other way (the dense leaves' transposed back step):
+ *   W[iidx[e ni + k]] -= sum_{j < 4, in order} coef[e cstride + ipat[j ni + k]] x_b(e, brow[j ni + k])
+ * for elements e < nelem, interior unknowns k < ni; ipat = -1: no coupling (skipped, brow not read);
+ * x_b(e, r) = W[bidx[e nb + r]], zero where bidx = -1 (a Dirichlet node).  The boundary entries read are not
+ * targets.  Deterministic; device memory; stream-ordered. */
+int sem_leaf_sparse_t(int nelem, int ni, int nb, const double* coef, int64_t cstride, const int32_t* ipat,
+                      const int32_t* brow, const int32_t* iidx, const int32_t* bidx, double* W, void* stream);
+/* The split leaves' transposed step in ONE launch, one workgroup per element, from sem_leaf_forward's blobs (same
+ * layout, same bounds):
+ *   r = b_i - A_bi^T x_b;  t = A_uu^-T r_u;  z_v = S_v^-T (r_v - D1 t);  z_u = t - A_uu^-T (D2 z_v)
+ * (the forward recipe with D1 and D2 swapped and both inverses applied transposed), A_uu^-1's register fragment
+ * loaded once for its two products; [z_u; z_v] is written to W[iidx[e 2n + .]].  A_bi^T x_b is formed as in
+ * sem_leaf_sparse_t with ni = 2n, k in [u; v] order and coef the blob's coef section (ipat = q nb + r).  The pad
+ * column of an odd n is loaded but its products are discarded (it may hold anything); the pad entries of D1, D2 are
+ * not read.  Each output column is summed over a thread's rows r = rs + 32 k (k increasing), then over rs = 0..31
+ * in order: bitwise repeatable.  Device memory; stream-ordered. */
+typedef struct sem_leaf_t_launch {
+  int nelem, n, ld, nb, nnz;
+  int64_t stride;
+  const double* blob;
+  const int32_t* iidx;
+  const int32_t* bidx;
+  const int32_t* ipat;
+  const int32_t* brow;
+  double* W;
+} sem_leaf_t_launch;
+int sem_leaf_transpose(const sem_leaf_t_launch* d, void* stream);
+
 /* ---- GMRES least-squares column (host) ------------------------------------ */
 /* Host memory, no device work (ABI 11): applies the Givens rotations 0..k-1 (cs, sn) to col[0..k+1], forms
  * rotation k from (col[k], col[k+1]) into cs[k], sn[k], applies it to col and to the rotated right-hand side

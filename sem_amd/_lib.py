@@ -77,6 +77,22 @@ class SemLeafLaunch(C.Structure):
                 ("W", C.c_void_p), ("stage", C.c_void_p), ("sstride", C.c_int64), ("soff", C.c_int64)]
 
 
+FRONT_T_MAX_PARTS = 16
+
+
+class SemFrontTLaunch(C.Structure):
+    _fields_ = [("ntiles", C.c_int), ("lanes", C.c_int), ("nparts", C.c_int), ("kmax", C.c_int), ("back", C.c_int),
+                ("op", C.c_void_p), ("dims", C.c_void_p), ("xoff", C.c_void_p), ("yoff", C.c_void_p),
+                ("poff", C.c_void_p), ("tiles", C.c_void_p), ("xidx", C.c_void_p), ("yidx", C.c_void_p),
+                ("W", C.c_void_p), ("stage", C.c_void_p), ("partials", C.c_void_p)]
+
+
+class SemLeafTLaunch(C.Structure):
+    _fields_ = [("nelem", C.c_int), ("n", C.c_int), ("ld", C.c_int), ("nb", C.c_int), ("nnz", C.c_int),
+                ("stride", C.c_int64), ("blob", C.c_void_p), ("iidx", C.c_void_p), ("bidx", C.c_void_p),
+                ("ipat", C.c_void_p), ("brow", C.c_void_p), ("W", C.c_void_p)]
+
+
 # name -> (restype, argtypes); mirrors include/sem_ops.h one-for-one
 _SIGS = {
     "sem_abi_version": (C.c_int, []),
@@ -138,6 +154,10 @@ _SIGS = {
                                         C.c_int64, C.c_void_p]),
     "sem_front_scatter": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "sem_front_gemv_t": (C.c_int, [C.POINTER(SemFrontTLaunch), C.c_void_p]),
+    "sem_leaf_sparse_t": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sem_leaf_transpose": (C.c_int, [C.POINTER(SemLeafTLaunch), C.c_void_p]),
     "sem_gemv_rows": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_double,
                                 C.c_void_p, C.c_void_p]),
 }

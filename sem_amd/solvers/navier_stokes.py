@@ -473,6 +473,50 @@ class NavierStokesSolver:
         self._part.assemble(ru, rv)
         return torch.stack((ru.view(-1, NY), rv.view(-1, NY)), dim=1).reshape(-1, 2 * NY)
 
+    def _whole_mesh_only(self, what):
+        if self._part is not None:
+            raise ValueError(f"NavierStokes: {what} is implemented for whole-mesh solvers only "
+                             "(no transposed strip apply, no transposed strip solve)")
+
+    def _velocity_apply_lines_T(self, X):
+        """J_D^T X for the velocity Jacobian of this linearisation on (NX, 2 NY) line arrays (the transpose of
+        _velocity_apply_lines' operator): with z' = (1 - m) z (m the Dirichlet mask),
+            u block: (Sys + diag(juu))_D^T z_u + jvu z'_v,    v block: (Sys + diag(jvv))_D^T z_v + juv z'_u
+        -- two fused transposed launches (sem_apply_transpose, identity Dirichlet rows), the cross terms pre-loaded
+        into the outputs and added through c_acc = 1.  The operator of check_refinement_T and of the transposed
+        velocity solve's refinement step.  Whole mesh only; sem_apply_transpose refuses what it does not support."""
+        self._whole_mesh_only("_velocity_apply_lines_T")
+        m, NY = self._mesh, self._mesh.NY
+        kw = self._jac_kw
+        sys = {k: kw[k] for k in ("c_stiff", "c_mass", "c_gradx", "cu", "c_grady", "cv")}
+        if getattr(self, "_free", None) is None:   # 1 - m on the device
+            self._free = m.to_device((~self._dir.mask_np).astype(np.float64))
+        zu, zv = X[:, :NY].reshape(-1).contiguous(), X[:, NY:].reshape(-1).contiguous()
+        yu, yv = kw["jvu"] * (self._free * zv), kw["juv"] * (self._free * zu)
+        m.apply_transpose(zu, yu, diag=kw["juu"], c_acc=1.0, dir_mode=_lib.DIR_IDENTITY, **sys, **self._dir.kw())
+        m.apply_transpose(zv, yv, diag=kw["jvv"], c_acc=1.0, dir_mode=_lib.DIR_IDENTITY, **sys, **self._dir.kw())
+        return torch.stack((yu.view(-1, NY), yv.view(-1, NY)), dim=1).reshape(-1, 2 * NY)
+
+    def velocity_solve_T(self, bu, bv):
+        """(J^-T [bu; bv]) split as (xu, xv) from the cached nested-dissection factor of _velocity_solver() -- the
+        inner solve of a transposed Schur matvec S_p^T = G^T J^-T D^T.  The first call after a linearisation
+        registers _velocity_apply_lines_T, runs check_refinement_T and, with velocity_graph, captures the transposed
+        solve.  NumPy in, NumPy out; device tensors in, device tensors out.  Whole-mesh solvers whose factor is
+        nested dissection only: there is no transposed line condensation and no transposed strip solve."""
+        self._whole_mesh_only("velocity_solve_T")
+        vs = self._velocity_solver()
+        if not isinstance(vs, NestedDissectionSolver):
+            raise ValueError("NavierStokes: velocity_solve_T needs the nested-dissection factor (P >= 2, the whole "
+                             "perimeter Dirichlet, velocity_interior 'auto' or 'nd'): the line condensation has no "
+                             "transposed solve")
+        if vs._apply_T is None:
+            vs.set_operator(self._velocity_apply_lines, apply_lines_T=self._velocity_apply_lines_T)
+            vs.check_refinement_T()
+            if self._velocity_graph:
+                vs.capture_T()
+        xu, xv = vs.solve_T(self._dev(bu), self._dev(bv))
+        return self._out(xu, bu), self._out(xv, bu)
+
     def _pressure_laplacian(self):
         """A_p = K with the pinned pressure row as an identity row (the Neumann pressure Laplacian
         made regular), factored once per solver by the one-component line condensation."""

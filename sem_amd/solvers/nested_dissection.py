@@ -37,6 +37,11 @@ Bytes per solve (cfg5: 128^2 elements, P = 12): the split leaves' blobs and V_e,
 (17.2 with Xi leaves) against the line condensation's 42.3 (model: tools/nd_model.py).  Strips use it too
 (StripNDSolver).  The algebra runs on any torch device: the CPU path (a per-front loop over the same tables) is
 what the CPU tests check against SciPy's sparse solve.
+
+The same factor solves J^T x = b (solve_T, solve1_T, capture_T, check_refinement_T): the transposed factors applied
+in the reverse order over the stored operators (_build_steps_T; HIP steps in csrc/front_transpose.hip), no operator
+stored twice, the plan built on the first transposed solve.  Whole mesh only: StripNDSolver refuses (no transposed
+reduced system), as does the line condensation (no transposed condensation).
 """
 import functools
 import math
@@ -274,7 +279,8 @@ def _gll_tables(P):
 
 class NestedDissectionSolver(VelocityJacobianSolver):
     """x = J^-1 b for the velocity Jacobian J of one linearisation by nested dissection (module docstring).  Same
-    interface as VelocityJacobianSolver (solve, solve1, _solve_lines, set_operator, check_refinement, capture);
+    interface as VelocityJacobianSolver (solve, solve1, _solve_lines, set_operator, check_refinement, capture), plus
+    the transposed solve J^-T b from the same factor (solve_T, solve1_T, _solve_lines_T, check_refinement_T, capture_T);
     factor with factor_mesh(mesh, **kw) (the device mesh) or factor_coeffs(dx, dy, **kw) (any torch device)."""
 
     def __init__(self, P, nex, ney, device, ncomp=2, cols=None):
@@ -285,6 +291,11 @@ class NestedDissectionSolver(VelocityJacobianSolver):
         self.interior = "nd"
         self.tree = nd_tree(P, nex, ney, ncomp, xa, xb)
         self.chunk_elems = int(os.environ.get("SEM_ND_CHUNK", "2048"))
+        # transposed solve (solve_T): its plan is built on first use; refine_T is check_refinement_T's gate
+        self._steps_T = self._hip_T = self._stage_T = self._graph_T = None
+        self._apply_T = None
+        self.refine_T = False
+        self.refine_eta_T = None
 
     # ------------------------------------------------------------------ factorisation
     def factor_mesh(self, mesh, budget_bytes=24 << 30, **kw):
@@ -586,6 +597,114 @@ class NestedDissectionSolver(VelocityJacobianSolver):
                                   st[3]["nitems"] * st[3]["stride"] if st[3] else 0) if st[0] == "fwd" else
                               st[1]["nelem"] * st[1]["sstride"] for st in steps if st[0] != "back")
         self._hip = self._hip_plan() if self.device.type == "cuda" else None
+        # the transposed plan (solve_T) is built on its first use: _build_steps_T
+        self._steps_T = self._hip_T = self._stage_T = None
+        self._graph_T = None
+
+    def _inverse_pattern(self, order, cidx):
+        """A_bi^T on A_bi's pattern read the other way: for interior unknown k (position order[k] in the element's
+        interior order) its four boundary couplings -- the two ends of its line and of its column, same component --
+        as (ipat, brow) (4, len(order)): cidx(r, q) of the coefficient and the boundary row r, rows increasing (the
+        fixed summation order); corners couple to no interior unknown."""
+        t = self.tree
+        P, ni = t.P, t.ni
+        cnt = np.zeros(ni, dtype=np.int64)
+        ipat = np.full((4, ni), -1, dtype=np.int64)
+        brow = np.zeros((4, ni), dtype=np.int64)
+        for r in range(t.nb):
+            i, j = t.pos_i[ni + r], t.pos_j[ni + r]
+            if (i in (0, P)) and (j in (0, P)):
+                continue
+            for q in range(P - 1):
+                k = t.bpat[r, q]
+                ipat[cnt[k], k] = cidx(r, q)
+                brow[cnt[k], k] = r
+                cnt[k] += 1
+        if cnt.max(initial=0) > 4:
+            raise AssertionError("nested dissection: an interior unknown with more than four boundary couplings")
+        return ipat[:, order], brow[:, order]
+
+    def _build_steps_T(self):
+        """The transposed solve J^T x = b over the same stored operators, as a step list beside _steps (built on the
+        first transposed solve: the forward plan, its tables and the factor are not touched).  J = L U in the
+        forward solve's product form, so J^-T applies the transposed factors in the reverse order:
+          ("gemvT", items, scatter, back): item (T, q, r0, r1, xidx, out): y = T[q][r0:r1]^T W[xidx] (the operands
+              are the operator's ROWS); back = False: stage[out : out + K] = y, then the scatter; back = True:
+              W[out] -= y.
+          ("sparseT", tables): dense leaves, W[i] -= A_bi^T x_b on the inverse pattern (x_b = 0 at Dirichlet nodes).
+          ("leafT", tables): split leaves, W[i] = A_ii^-T (W[i] - A_bi^T x_b) from the forward blobs.
+        Order: leaves W[b] -= V_e^T W[i]; fronts from the deepest level, y_S = Fw[:s]^T W[S] and W[B] -= V^T W[S];
+        fronts from the root, W[S] -= Fw[s:]^T W[B]; leaves; last the transposed lift onto the Dirichlet nodes
+        (x_D = b_D - A_ND^T x_N)."""
+        t = self.tree
+        ni, ne, nb = t.ni, t.ne, t.nb
+        E = self.nex * self.ney
+        none = np.zeros(0, np.int64)
+        steps = []
+        items, bt, bs = [], [], []
+        for e in range(E):
+            items.append((self._leafV, e, 0, ni, t.eflat[e, :ni], e * nb))
+            keep = ~t.eD[e, ni:]
+            bt.append(t.eflat[e, ni:][keep])
+            bs.append(e * nb + np.nonzero(keep)[0])
+        steps.append(("gemvT", items, self._scatter_plan(none, none, np.concatenate(bt), np.concatenate(bs)), False))
+        levels = {}
+        for fid, f in enumerate(t.fronts):
+            levels.setdefault(f["depth"], []).append(fid)
+        for depth in sorted(levels, reverse=True):
+            items, ct, cs, bt, bs = [], [], [], [none], [none]
+            off = 0
+            for fid in levels[depth]:
+                f = t.fronts[fid]
+                s, b = len(f["S"]), len(f["B"])
+                Fw, q = self._fw[fid]
+                items.append((Fw, q, 0, s, f["S"], off))
+                ct.append(f["S"])
+                cs.append(off + np.arange(s))
+                if b:
+                    V, qv = self._fv[fid]
+                    items.append((V, qv, 0, s, f["S"], off + s))
+                    bt.append(f["B"])
+                    bs.append(off + s + np.arange(b))
+                off += s + b
+            steps.append(("gemvT", items, self._scatter_plan(np.concatenate(ct), np.concatenate(cs),
+                                                             np.concatenate(bt), np.concatenate(bs)), False))
+        for depth in sorted(levels):
+            items = []
+            for fid in levels[depth]:
+                f = t.fronts[fid]
+                s, b = len(f["S"]), len(f["B"])
+                if b:
+                    Fw, q = self._fw[fid]
+                    items.append((Fw, q, s, s + b, f["B"], f["S"]))
+            if items:
+                steps.append(("gemvT", items, None, True))
+        bidx = np.where(t.eD[:, ni:], -1, t.eflat[:, ni:])
+        if self.split:
+            n = (self.P - 1) ** 2
+            perm = t.split_perm()
+            ipat, brow = self._inverse_pattern(perm, lambda r, q: q * nb + r)
+            steps.append(("leafT", dict(iidx=t.eflat[:, perm], bidx=bidx, ipat=ipat, brow=brow, n=n, nb=nb, nelem=E)))
+        else:
+            ipat, brow = self._inverse_pattern(np.arange(ni), lambda r, q: r * (self.P - 1) + q)
+            steps.append(("sparseT", dict(coef=self._leafAc, iidx=t.eflat[:, :ni], bidx=bidx, ipat=ipat, brow=brow,
+                                          nelem=E)))
+            items = [(self._leafF, e, 0, ni, t.eflat[e, :ni], e * ni) for e in range(E)]
+            steps.append(("gemvT", items, self._scatter_plan(t.eflat[:, :ni].reshape(-1), np.arange(E * ni), none,
+                                                             none), False))
+        if len(self._per):
+            items, tgt, src = [], [], []
+            for q, e in enumerate(self._per):
+                items.append((self._lift, q, 0, ne, np.where(t.eD[e], -1, t.eflat[e]), q * nb))
+                dn = t.eD[e, ni:]
+                tgt.append(t.eflat[e, ni:][dn])
+                src.append(q * nb + np.nonzero(dn)[0])
+            steps.append(("gemvT", items, self._scatter_plan(none, none, np.concatenate(tgt), np.concatenate(src)),
+                          False))
+        self._stage_len_T = max(max(it[5] + it[0].shape[2] for it in st[1]) for st in steps
+                                if st[0] == "gemvT" and not st[3])
+        self._steps_T = steps
+        self._hip_T = self._hip_plan_T() if self.device.type == "cuda" else None
 
     @staticmethod
     def _scatter_plan(copy_tgt, copy_src, acc_tgt, acc_src):
@@ -658,6 +777,367 @@ class NestedDissectionSolver(VelocityJacobianSolver):
                     x = Wz[torch.as_tensor(xidx, device=dev)]
                     y = torch.as_tensor(yidx, device=dev)
                     Wz[y] = Wz[y] - T[q] @ x
+
+    # ------------------------------------------------------------------ transposed solve
+    def _solve_lines_once_T(self, B):
+        """x = J^-T b on line arrays: the transposed steps (_build_steps_T, built here on the first call) -- on the
+        device the HIP launches, elsewhere the torch loop over the same tables.  A solver's forward and transposed
+        solves are stream-ordered, not concurrent (they work on the same factor and are launched on one stream)."""
+        if self._steps_T is None:
+            self._build_steps_T()
+        Wz = torch.cat((B.reshape(-1), B.new_zeros(1)))
+        if self.device.type == "cuda":
+            self._run_hip_T(Wz)
+        else:
+            self._run_T(Wz)
+        return Wz[:-1].view(self.NX, self.m)
+
+    @staticmethod
+    def _sparse_T(Wz, coef, L, dev):
+        """sum_j coef[e, ipat[j, k]] x_b[e, brow[j, k]] per (element, interior unknown k), j = 0..3 in order."""
+        ipat, brow = (torch.as_tensor(L[k], device=dev) for k in ("ipat", "brow"))
+        xb = Wz[torch.as_tensor(L["bidx"], device=dev)]            # -1: the trailing zero
+        acc = None
+        for j in range(4):
+            term = torch.where(ipat[j] >= 0, coef[:, ipat[j].clamp(min=0)] * xb[:, brow[j]],
+                               torch.zeros((), dtype=Wz.dtype, device=dev))
+            acc = term if acc is None else acc + term
+        return acc
+
+    def _run_T(self, Wz, lo=0, hi=None):
+        stage = Wz.new_zeros(self._stage_len_T)
+        dev = Wz.device
+        for st in self._steps_T[lo:hi]:
+            if st[0] == "sparseT":
+                L = st[1]
+                ii = torch.as_tensor(L["iidx"], device=dev)
+                Wz[ii] = Wz[ii] - self._sparse_T(Wz, L["coef"].reshape(L["nelem"], -1), L, dev)
+            elif st[0] == "leafT":   # the split leaves (sem_leaf_transpose), batched over the elements
+                L = st[1]
+                n = L["n"]
+                Au, Sv, d1, d2, cT = self._blob_views(self._leafB)
+                ii = torch.as_tensor(L["iidx"], device=dev)
+                r = Wz[ii] - self._sparse_T(Wz, cT.reshape(L["nelem"], -1), L, dev)
+                AuT = Au.transpose(1, 2)
+                tt = (AuT @ r[:, :n, None])[..., 0]
+                zv = (Sv.transpose(1, 2) @ (r[:, n:] - d1 * tt)[..., None])[..., 0]
+                zu = tt - (AuT @ (d2 * zv)[..., None])[..., 0]
+                Wz[ii.reshape(-1)] = torch.cat((zu, zv), 1).reshape(-1)
+            elif st[3]:
+                for T, q, r0, r1, xidx, yidx in st[1]:
+                    x = Wz[torch.as_tensor(xidx, device=dev)]
+                    y = torch.as_tensor(yidx, device=dev)
+                    Wz[y] = Wz[y] - T[q, r0:r1].t() @ x
+            else:
+                for T, q, r0, r1, xidx, off in st[1]:
+                    x = Wz[torch.as_tensor(xidx, device=dev)]
+                    stage[off:off + T.shape[2]] = T[q, r0:r1].t() @ x
+                sc = st[2]
+                ct, cs, at, a4 = (torch.as_tensor(sc[k], device=dev) for k in ("copy_tgt", "copy_src", "acc_tgt",
+                                                                                "acc_src"))
+                Wz[ct] = stage[cs]
+                v = Wz[at]
+                for k in range(4):
+                    s = a4[:, k]
+                    v = v - torch.where(s >= 0, stage[s.clamp(min=0)], torch.zeros_like(v))
+                Wz[at] = v
+
+    def _solve_lines_T(self, B):
+        """x = J^-T b with b, x as (NX, ncomp NY) line arrays; with `refine_T` set, one step of iterative refinement
+        on the transposed matrix-free apply (set_operator's apply_lines_T)."""
+        X = self._solve_lines_once_T(B)
+        if self.refine_T:
+            if self._apply_T is None:
+                raise RuntimeError("refine_T is set but no transposed operator: set_operator(..., apply_lines_T=...)")
+            X = X + self._solve_lines_once_T(B - self._apply_T(X))
+        return X
+
+    def set_operator(self, apply_lines, amax=None, apply_lines_T=None):
+        """As VelocityJacobianSolver.set_operator; apply_lines_T(X) -> J^T X on (NX, m) line arrays is the operator of
+        check_refinement_T and of the transposed solve's refinement step."""
+        super().set_operator(apply_lines, amax)
+        self._apply_T = apply_lines_T
+
+    def check_refinement_T(self, tau=None, seed=17):
+        """check_refinement's twin for J^T x = b: the transposed solve's normwise backward error on a seeded probe
+        (||J^T|| from below by ||J^T s|| for a random sign vector), refine_T = eta > tau (SEM_REFINE_ETA, default
+        1e-13), refine_eta_T = eta; a non-finite eta raises.  Returns eta."""
+        if self._apply_T is None:
+            raise RuntimeError("set_operator(..., apply_lines_T=...) first")
+        if self._amax is None:
+            self._amax = lambda t: float(t.abs().max())
+        if tau is None:
+            tau = float(os.environ.get("SEM_REFINE_ETA", "1e-13"))
+        g = torch.Generator(device=self.device).manual_seed(seed)
+        b = torch.rand((self.NX, self.m), dtype=torch.float64, device=self.device, generator=g) * 2 - 1
+        sgn = torch.sign(torch.rand((self.NX, self.m), dtype=torch.float64, device=self.device, generator=g) - 0.5)
+        self.refine_T = False
+        nJ = self._amax(self._apply_T(sgn))
+        x = self._solve_lines_T(b)
+        eta = self._amax(b - self._apply_T(x)) / (nJ * self._amax(x) + self._amax(b))
+        if not math.isfinite(eta):
+            raise RuntimeError(f"velocity factor: non-finite backward error on the transposed probe ({eta}): a "
+                               "singular or overflowing pivot block")
+        self.refine_eta_T = eta
+        self.refine_T = eta > tau
+        return eta
+
+    def capture_T(self):
+        """Capture the transposed solve in a second hipGraph with its own input and output buffers (capture()'s
+        twin; solve_T / solve1_T replay it).  Forward and transposed solves of one solver are stream-ordered, not
+        concurrent.  Returns False (the transposed solve stays eager) if the capture is refused."""
+        if self.device.type != "cuda" or not self.factored:
+            return False
+        from .velocity_solve import no_gc
+        self._bin_T = torch.zeros((self.NX, self.m), dtype=torch.float64, device=self.device)
+        cur = torch.cuda.current_stream(self.device)
+        s = torch.cuda.Stream(self.device)
+        s.wait_stream(cur)
+        try:
+            with torch.cuda.stream(s):
+                self._solve_lines_T(self._bin_T)      # builds the plan and warms up outside the capture
+            cur.wait_stream(s)
+            g = torch.cuda.CUDAGraph()
+            with no_gc(), torch.cuda.graph(g):
+                self._xout_T = self._solve_lines_T(self._bin_T)
+            self._graph_T = g
+            return True
+        except RuntimeError:
+            torch.cuda.synchronize(self.device)
+            self._graph_T = None
+            return False
+
+    def solve1_T(self, b):
+        """x = A^-T b for a one-component operator; b is a length-N vector in the x-major numbering."""
+        if not self.factored:
+            raise RuntimeError("factor() first")
+        if self.ncomp != 1:
+            raise ValueError("solve1_T needs ncomp=1")
+        NX, NY = self.NX, self.NY
+        if self._graph_T is not None:
+            self._bin_T.copy_(b.reshape(NX, NY))
+            self._graph_T.replay()
+            return self._xout_T.reshape(-1).clone()
+        return self._solve_lines_T(b.reshape(NX, NY).clone()).reshape(-1)
+
+    def solve_T(self, bu, bv):
+        """(J^-T [bu; bv]) split as (xu, xv), from the same factor as solve (no second copy of the operators)."""
+        if not self.factored:
+            raise RuntimeError("factor() first")
+        if self.ncomp != 2:
+            raise ValueError("solve_T needs ncomp=2; use solve1_T")
+        NX, NY = self.NX, self.NY
+        if self._graph_T is not None:
+            b3 = self._bin_T.view(NX, 2, NY)
+            b3[:, 0, :] = bu.reshape(NX, NY)
+            b3[:, 1, :] = bv.reshape(NX, NY)
+            self._graph_T.replay()
+            out = self._xout_T.view(NX, 2, NY)
+            return out[:, 0, :].reshape(-1).clone(), out[:, 1, :].reshape(-1).clone()
+        B = torch.stack((bu.reshape(NX, NY), bv.reshape(NX, NY)), dim=1).reshape(NX, self.m)
+        out = self._solve_lines_T(B).view(NX, 2, NY)
+        return out[:, 0, :].reshape(-1), out[:, 1, :].reshape(-1)
+
+    # sem_front_gemv_t from this median operand-row count on (_launch_form_T)
+    T_MIN_ROWS = 48
+
+    def _launch_form_T(self, K, R):
+        """The kernel of one transposed GEMV launch (`forms_T` = "auto"; "cols" / "t": one form wherever it can run):
+        "t" (sem_front_gemv_t: lanes along the stored rows' columns, the operand rows split over row groups and
+        parts) or "cols" (sem_front_gemv's column form handed the untransposed storage: a thread per output walks
+        all operand rows serially).  Rule, from the per-launch A/B of the two plans alternated in one process
+        (tools/nd_probe.py --transpose 1; profiles/nd_transpose/, min-max of five runs in us, "t" against "cols"):
+          * median operand rows R < T_MIN_ROWS: "cols".  Nothing to split: cfg5 R = 22 94-99 against 83-85; R = 46
+            level at cfg4 and on one of two cfg5 levels.
+          * full column workgroups that fill the device (median K >= 256 outputs and >= 256 workgroups of 256
+            outputs): "cols".  cfg5's forward levels of 128-512 fronts, R = 190-382: 68-69 against 62-64, the others
+            level.
+          * else "t": ahead from R ~ 94 on (cfg5 R = 94 55-58 against 61-64; the back levels of 8192-128 fronts 49-50
+            against 69-71 to 56-58 against 97-98) and by 3-10x on the top levels (cfg5 root 25-26 against 240-243,
+            cfg4 root 16 against 65), where the column form has a handful of workgroups each walking every row."""
+        forms = getattr(self, "forms_T", "auto")
+        if forms == "cols":
+            return "cols"
+        if forms == "t":
+            return "t"
+        if int(np.median(R)) < self.T_MIN_ROWS:
+            return "cols"
+        if int(np.median(K)) >= 256 and int(((K + 255) // 256).sum()) >= 256:
+            return "cols"
+        return "t"
+
+    @staticmethod
+    def _launch_shape_T(K, R):
+        """(lanes, nparts) of sem_front_gemv_t: lanes = the launch's median column-pair count rounded up to a power
+        of two in 4..64 (a row's pairs fill the lanes of one column tile); the operand rows are split over parts only
+        where the launch would otherwise have fewer than 256 workgroups (the top levels: one or two fronts), towards
+        512 workgroups, a part keeping at least 64 rows."""
+        from .. import _lib
+        kp = max(1, int(np.median(K)) // 2)
+        lanes = max(4, min(64, 1 << (kp - 1).bit_length()))
+        tiles = int(((K + 2 * lanes - 1) // (2 * lanes)).sum())
+        nparts = 1
+        if tiles < 256:
+            nparts = max(1, min(_lib.FRONT_T_MAX_PARTS, -(-512 // tiles), int(np.median(R)) // 64))
+        return lanes, nparts
+
+    def _hip_plan_T(self):
+        """Device tables of the transposed steps, checked on the host against the line array and the stage buffer
+        before anything is launched (as _hip_plan).  The transposed solve has its own stage buffer."""
+        from .. import _lib
+        dev = self.device
+        nW = self.NX * self.m
+        self._stage_T = torch.zeros(self._stage_len_T, dtype=torch.float64, device=dev)
+        P, nb = self.P, self.tree.nb
+
+        def i32(a):
+            a = np.ascontiguousarray(a, dtype=np.int64)
+            if a.size and (a.min() < -1 or a.max() >= 2 ** 31 - 1):
+                raise AssertionError("nested dissection: index outside int32")
+            return torch.as_tensor(a.astype(np.int32), device=dev)
+
+        def leaf_tables(L, ncoef, nint):
+            iidx, bidx, ipat, brow = (np.asarray(L[k]) for k in ("iidx", "bidx", "ipat", "brow"))
+            E = L["nelem"]
+            if (iidx.shape != (E, nint) or iidx.min() < 0 or iidx.max() >= nW or len(np.unique(iidx)) != iidx.size
+                    or bidx.shape != (E, nb) or bidx.min() < -1 or bidx.max() >= nW
+                    or np.isin(bidx[bidx >= 0], iidx).any() or ipat.shape != (4, nint) or brow.shape != (4, nint)
+                    or ipat.min() < -1 or ipat.max() >= ncoef or brow.min() < 0 or brow.max() >= nb):
+                raise AssertionError("nested dissection: bad transposed leaf step")
+            return dict(iidx=i32(iidx), bidx=i32(bidx), ipat=i32(ipat), brow=i32(brow))
+
+        plan, npart = [], 0
+        for st in self._steps_T:
+            if st[0] == "leafT":
+                L, B = st[1], self._leafB
+                n, E = L["n"], L["nelem"]
+                ld = n + (n & 1)
+                if (not 1 <= n <= 121 or B.shape != (E, 2 * n * ld + 2 * ld + (P - 1) * nb) or not B.is_contiguous()
+                        or B.data_ptr() % 16 or B.shape[1] % 2 or B.device != dev):
+                    raise AssertionError("nested dissection: bad split-leaf blobs")
+                keep = leaf_tables(L, (P - 1) * nb, 2 * n)
+                d = _lib.SemLeafTLaunch(E, n, ld, nb, P - 1, B.shape[1], B.data_ptr(), keep["iidx"].data_ptr(),
+                                        keep["bidx"].data_ptr(), keep["ipat"].data_ptr(), keep["brow"].data_ptr(), None)
+                plan.append(("leafT", d, keep, None))
+                continue
+            if st[0] == "sparseT":
+                L = st[1]
+                coef = L["coef"]
+                if (tuple(coef.shape) != (L["nelem"], nb, P - 1) or not coef.is_contiguous() or coef.device != dev
+                        or coef.dtype != torch.float64):
+                    raise AssertionError("nested dissection: bad dense-leaf coupling coefficients")
+                keep = leaf_tables(L, nb * (P - 1), self.tree.ni)
+                plan.append(("sparseT", (L["nelem"], self.tree.ni, nb, coef.data_ptr(), nb * (P - 1)), keep, None))
+                continue
+            items, back = st[1], st[3]
+            nf = len(items)
+            ptr = np.empty(nf, dtype=np.int64)
+            dims = np.zeros((nf, 4), dtype=np.int64)
+            xoff = np.zeros(nf, dtype=np.int64)
+            yoff = np.zeros(nf, dtype=np.int64)
+            xs, ys = [], []
+            xo = yo = 0
+            for k, (T, q, r0, r1, xidx, out) in enumerate(items):
+                ld = T.shape[2]
+                if T.stride(2) != 1 or T.stride(1) != ld or T.dtype != torch.float64 or T.device != dev:
+                    raise AssertionError("nested dissection: operators must be contiguous float64 rows")
+                if not (0 <= q < T.shape[0] and 0 <= r0 < r1 <= T.shape[1]):
+                    raise AssertionError("nested dissection: operator rows outside their group")
+                ptr[k] = T.data_ptr() + (q * T.stride(0) + r0 * ld) * 8
+                if ld % 2 or ptr[k] % 16:       # as the forward plan: 16-byte pairs
+                    raise AssertionError("nested dissection: operator rows must be 16-byte aligned and of even length")
+                dims[k, :3] = (r1 - r0, ld, ld)       # operand rows, output columns, leading dimension
+                if len(xidx) != r1 - r0:
+                    raise AssertionError("nested dissection: operand count differs from the operator height")
+                xoff[k] = xo
+                xs.append(xidx)
+                xo += r1 - r0
+                if back:
+                    if len(out) != ld:
+                        raise AssertionError("nested dissection: target count differs from the operator width")
+                    yoff[k] = yo
+                    ys.append(out)
+                    yo += ld
+                else:
+                    if out < 0 or out + ld > self._stage_len_T:
+                        raise AssertionError("nested dissection: stage overflow")
+                    yoff[k] = out
+            R, K = dims[:, 0], dims[:, 1]
+            if int(R.max()) > 8192:
+                raise ValueError("nested dissection: a front with more than 8192 operands (sem_front_gemv stages them "
+                                 "in LDS); the mesh is too large for this dissection")
+            xidx = np.concatenate(xs)
+            if xidx.size and (xidx.min() < -1 or xidx.max() >= nW):
+                raise AssertionError("nested dissection: operand index outside the line array")
+            yidx = None
+            if back:
+                yidx = np.concatenate(ys)
+                if (yidx.min() < 0 or yidx.max() >= nW or len(np.unique(yidx)) != len(yidx)
+                        or np.isin(yidx, xidx).any()):
+                    raise AssertionError("nested dissection: back-substitution targets must be distinct line entries "
+                                         "and no operands of the launch")
+            form = self._launch_form_T(K, R)
+            keep = dict(ptr=torch.as_tensor(ptr, device=dev), xoff=torch.as_tensor(xoff, device=dev),
+                        yoff=torch.as_tensor(yoff, device=dev), xidx=i32(xidx), yidx=i32(yidx) if back else None)
+            yptr = keep["yidx"].data_ptr() if back else None
+            sptr = None if back else self._stage_T.data_ptr()
+            if form == "cols":      # sem_front_gemv form 1 reads "A^T rows": the stored rows are those of (A^T)^T
+                nt = (K + 255) // 256
+                tiles = np.stack((np.repeat(np.arange(nf), nt), np.concatenate([np.arange(n) * 256 for n in nt])), 1)
+                keep.update(dims=i32(np.stack((K, R, dims[:, 2], dims[:, 3]), 1)), tiles=i32(tiles))
+                d = _lib.SemFrontLaunch(len(tiles), 256, 1, int(R.max()), int(back), 1, keep["ptr"].data_ptr(),
+                                        keep["dims"].data_ptr(), keep["xoff"].data_ptr(), keep["yoff"].data_ptr(),
+                                        keep["tiles"].data_ptr(), keep["xidx"].data_ptr(), yptr, None, sptr)
+            else:
+                lanes, nparts = self._launch_shape_T(K, R)
+                nt = (K + 2 * lanes - 1) // (2 * lanes)
+                tf = np.repeat(np.arange(nf), nt * nparts)
+                tc = np.concatenate([np.repeat(np.arange(n) * 2 * lanes, nparts) for n in nt])
+                tp = np.concatenate([np.tile(np.arange(nparts), n) for n in nt])
+                tiles = np.stack((tf, tc, tp, np.zeros_like(tf)), 1)
+                poff = np.concatenate(([0], np.cumsum(K * nparts)))
+                if nparts > 1:
+                    npart = max(npart, int(poff[-1]))
+                keep.update(dims=i32(dims), tiles=i32(tiles), poff=torch.as_tensor(poff[:-1].copy(), device=dev))
+                d = _lib.SemFrontTLaunch(len(tiles), lanes, nparts, int(R.max()), int(back), keep["ptr"].data_ptr(),
+                                         keep["dims"].data_ptr(), keep["xoff"].data_ptr(), keep["yoff"].data_ptr(),
+                                         keep["poff"].data_ptr(), keep["tiles"].data_ptr(), keep["xidx"].data_ptr(),
+                                         yptr, None, sptr, None)
+            sc = None if back else self._scatter_tables(st[2], nW, i32, self._stage_len_T)
+            plan.append(("gemvT", d, keep, sc))
+        self._partials_T = torch.zeros(max(npart, 1), dtype=torch.float64, device=dev)
+        for kind, d, _, _ in plan:
+            if kind == "gemvT" and isinstance(d, _lib.SemFrontTLaunch):
+                d.partials = self._partials_T.data_ptr()
+        return plan
+
+    def _run_hip_T(self, Wz, lo=0, hi=None):
+        """The transposed steps on the device: per step one GEMV launch (sem_front_gemv_t, or sem_front_gemv's column
+        form on the untransposed storage) and, after a stage-writing one, one sem_front_scatter; the leaves' step is
+        sem_leaf_transpose (split) or sem_leaf_sparse_t before their X_i^T product (dense)."""
+        import ctypes as C
+        from .. import _lib
+        lib = _lib.load()
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        for kind, d, keep, sc in self._hip_T[lo:hi]:
+            if kind == "leafT":
+                d.W = Wz.data_ptr()
+                _lib.check(lib.sem_leaf_transpose(C.byref(d), st))
+            elif kind == "sparseT":
+                nelem, ni, nb, coef, cstride = d
+                _lib.check(lib.sem_leaf_sparse_t(nelem, ni, nb, coef, cstride, keep["ipat"].data_ptr(),
+                                                 keep["brow"].data_ptr(), keep["iidx"].data_ptr(),
+                                                 keep["bidx"].data_ptr(), Wz.data_ptr(), st))
+            else:
+                d.W = Wz.data_ptr()
+                if isinstance(d, _lib.SemFrontTLaunch):
+                    _lib.check(lib.sem_front_gemv_t(C.byref(d), st))
+                else:
+                    _lib.check(lib.sem_front_gemv(C.byref(d), st))
+                if sc is not None:
+                    _lib.check(lib.sem_front_scatter(sc["n_copy"], sc["ct"].data_ptr(), sc["cs"].data_ptr(),
+                                                     sc["n_acc"], sc["at"].data_ptr(), sc["a4"].data_ptr(),
+                                                     self._stage_T.data_ptr(), Wz.data_ptr(), st))
 
     def _hip_plan(self):
         """Device tables of every step (sem_front_gemv descriptors, sem_front_scatter index arrays), checked on the
@@ -766,12 +1246,13 @@ class NestedDissectionSolver(VelocityJacobianSolver):
             plan.append((d, keep, sc, sp))
         return plan
 
-    def _scatter_tables(self, p, nW, i32):
+    def _scatter_tables(self, p, nW, i32, stage_len=None):
+        stage_len = self._stage_len if stage_len is None else stage_len
         for a, hi in ((p["copy_tgt"], nW), (p["acc_tgt"], nW)):
             if a.size and (a.min() < 0 or a.max() >= hi):
                 raise AssertionError("nested dissection: scatter target outside the line array")
         for a in (p["copy_src"], p["acc_src"]):
-            if a.size and (a.min() < -1 or a.max() >= self._stage_len):
+            if a.size and (a.min() < -1 or a.max() >= stage_len):
                 raise AssertionError("nested dissection: scatter source outside the stage")
         if len(np.unique(np.concatenate((p["copy_tgt"], p["acc_tgt"])))) != len(p["copy_tgt"]) + len(p["acc_tgt"]):
             raise AssertionError("nested dissection: scatter targets must be distinct")
@@ -907,6 +1388,13 @@ class StripNDSolver(_StripReduced, NestedDissectionSolver):
             idx = torch.as_tensor(side * m + np.nonzero(dmask)[0], device=self.device)
             R[idx, idx] = 1.0
         return R.view(2, m, 2, m).permute(0, 2, 1, 3).contiguous()
+
+    def _no_transpose(self, *a, **kw):
+        raise NotImplementedError("the strip nested-dissection solve has no transposed solve: no transposed reduced "
+                                  "system over the strip-boundary lines; solve_T needs the whole mesh in one "
+                                  "NestedDissectionSolver")
+
+    solve_T = solve1_T = _solve_lines_T = capture_T = check_refinement_T = _no_transpose
 
     def _between(self, W, B):
         if self.G == 1:

@@ -1246,6 +1246,13 @@ class VelocityJacobianSolver:
             return self._xout.reshape(-1).clone()
         return self._solve_lines(b.reshape(NX, NY).clone()).reshape(-1)
 
+    def solve_T(self, bu, bv):
+        """J^T x = b is not available from the line condensation: there is no transposed condensation (the nested
+        interior solves and the interface sweep would both have to run transposed).  The nested-dissection factor
+        has it (NestedDissectionSolver.solve_T)."""
+        raise NotImplementedError("the line-condensation velocity solve has no transposed solve: no transposed "
+                                  "condensation; factor with NestedDissectionSolver for solve_T")
+
     def solve(self, bu, bv):
         """(J^-1 [bu; bv]) split as (xu, xv); bu, bv are length-N vectors in the x-major numbering."""
         if not self.factored:
