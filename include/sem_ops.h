@@ -605,6 +605,38 @@ typedef struct sem_ns_desc {
 int sem_ns_apply(sem_handle* h, const sem_ns_desc* d, const double* u, const double* v, const double* p, double* ru,
                  double* rv, double* rc, void* stream);
 
+/* Fused transposed (adjoint) apply of sem_ns_apply's linear part: (yu, yv, yp) = A^T (zu, zv, zc) in one launch, for
+ * the 3N x 3N operator A that sem_ns_apply applies with T, dval_u, dval_v NULL and pin_val 0,
+ *     A = [ J  B ]   J = the velocity rows (Sys + j** blocks) with identity Dirichlet rows,  B = (1 - m) [G_x; G_y],
+ *         [ C  E ]   C = c_div (1 - m_c) [G_x, G_y],                                        E = diag(m_b) K + e_pin e_pin^T,
+ * m the Dirichlet set, m_c the rows of rc that are not divergence rows (m and the pin), m_b its (K p) rows (m without
+ * the pin; with pin_first a pin on a Dirichlet node stays a (K p) row, as in sem_ns_apply).  With z'_u = (1 - m) zu,
+ * z'_v = (1 - m) zv, w = c_div (1 - m_c) zc, k = m_b zc:
+ *     yu = Sys^T z'_u + juu z'_u + jvu z'_v + G_x^T w + m zu
+ *     yv = Sys^T z'_v + jvv z'_v + juv z'_u + G_y^T w + m zv
+ *     yp = G_x^T z'_u + G_y^T z'_v + K k + e_pin zc[pin]
+ *     yT = c_T M z'_v          (the adjoint of sem_ns_apply's c_T M T term: what rv's bar contributes to T's)
+ * The descriptor is sem_ns_desc unchanged, read as follows:
+ *   c_mass, c_stiff, c_gradx, c_grady, cu, cv, j**, c_T, c_div   as for sem_ns_apply
+ *   dir_mask, dir_sides, pin, pin_first                          as for sem_ns_apply
+ *   uv_pitch                                                     the layout of zu, zv, yu, yv (as of u, v, ru, rv);
+ *                                                                zc, yp, yT and every coefficient are plain vectors
+ *   T, dval_u, dval_v                                            must be NULL
+ *   pin_val                                                      must be 0
+ * A NULL input is zeros; a NULL output is not computed; with every output NULL the call returns SEM_OK and launches
+ * nothing.  Deterministic (one fixed summation order, no atomics: bitwise repeatable); nothing is allocated or
+ * synchronised, so the launch can be captured in a graph.  Three forms run kernels that form only the sums they use: the
+ * transposed gradient (zc in; yu, yv out), the transposed divergence (zu, zv, zc in; yp out) and the velocity rows
+ * (zu, zv in; yu, yv out).
+ * SEM_EINVAL: null h or d; non-NULL T / dval_u / dval_v or pin_val != 0; an output that is one of the inputs;
+ * cu or cv that is zu or zv while these are line views (uv_pitch neither 0 nor NY); uv_pitch below NY; pin outside
+ * [-1, N); a handle of another device than the current one.
+ * SEM_EUNSUPPORTED: a strip handle (ex_begin != 0 or ex_end != nex), P outside the compiled range (sem_create refuses
+ * such a handle the same way), or a mesh past the kernel's 32-bit node offsets (n_local or (NX - 1) uv_pitch + NY
+ * above 2^31 - 1). */
+int sem_ns_apply_transpose(sem_handle* h, const sem_ns_desc* d, const double* zu, const double* zv, const double* zc,
+                           double* yu, double* yv, double* yp, double* yT, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -270,6 +270,38 @@ class Mesh:
                                           *(_ptr(t) for t in views[2:]), _ptr(rc), self.stream_ptr(stream)))
         return views[2], views[3], rc
 
+    def ns_apply_transpose(self, zu=None, zv=None, zc=None, yu=None, yv=None, yp=None, yT=None, *, c_mass=0.0,
+                           c_stiff=0.0, c_gradx=0.0, c_grady=0.0, cu=None, cv=None, juu=None, juv=None, jvu=None,
+                           jvv=None, c_T=0.0, T=None, c_div=1.0, dval_u=None, dval_v=None, dir_mask=None, dir_sides=0,
+                           pin=-1, pin_val=0.0, pin_first=False, stream=None):
+        """Fused transposed apply of ns_apply's linear part (include/sem_ops.h, sem_ns_apply_transpose):
+        (yu, yv, yp) = A^T (zu, zv, zc) and yT = c_T M (1 - m) zv in one launch; returns (yu, yv, yp, yT).  zu, zv,
+        yu, yv are plain vectors or (NX, NY) line views sharing one row stride; a None input is zeros, a None output
+        is not computed.  Whole-mesh handles only.  T, dval_u, dval_v and pin_val are the descriptor fields the
+        transpose of the linear part does not take: the library refuses them as the header documents."""
+        pitch = set()
+        views = []
+        for nm, t in (("zu", zu), ("zv", zv), ("yu", yu), ("yv", yv)):
+            t, s = self._line_view(t, nm)
+            views.append(t)
+            if t is not None:
+                pitch.add(s)
+        if len(pitch) > 1:
+            raise ValueError("zu, zv, yu, yv must share one layout")
+        for nm, t in (("zc", zc), ("yp", yp), ("yT", yT), ("T", T), ("cu", cu), ("cv", cv), ("juu", juu), ("juv", juv),
+                      ("jvu", jvu), ("jvv", jvv), ("dval_u", dval_u), ("dval_v", dval_v)):
+            self._vec(t, nm)
+        if dir_mask is not None and (dir_mask.dtype != torch.uint8 or dir_mask.numel() != self.n_local):
+            raise ValueError("dir_mask must be a uint8 tensor of n_local entries")
+        d = _lib.SemNsDesc(float(c_mass), float(c_stiff), float(c_gradx), float(c_grady), _ptr(cu), _ptr(cv),
+                           _ptr(juu), _ptr(juv), _ptr(jvu), _ptr(jvv), float(c_T), _ptr(T), float(c_div),
+                           _ptr(dval_u), _ptr(dval_v), _ptr(dir_mask), int(dir_sides), int(bool(pin_first)), int(pin),
+                           float(pin_val), pitch.pop() if pitch else 0)
+        _lib.check(self._lib.sem_ns_apply_transpose(self._h, C.byref(d), *(_ptr(t) for t in views[:2]), _ptr(zc),
+                                                    *(_ptr(t) for t in views[2:]), _ptr(yp), _ptr(yT),
+                                                    self.stream_ptr(stream)))
+        return views[2], views[3], yp, yT
+
     # ------------------------------------------------------------------ host-side 1-D tables
     def weights_1d(self):
         """Assembled 1-D GLL weights over the locally held lines (x) and all columns (y)."""

@@ -106,13 +106,11 @@ def _fwd_only(mode):
         raise ValueError('only forward mode implemented')
 
 
-class ConvectionDiffusion_Component(_Base):
-    """OpenMDAO/ConvectionDiffusion_Component.py:6-61: output T_cd, inputs u_ns, v_ns."""
+class _AdjointOption(_Base):
+    """What the two components share beyond the reference: the `adjoint` option (the reference's components are
+    forward-mode only; reverse mode is opt-in and off by default)."""
 
-    def initialize(self):
-        self.options.declare('solver_CD', desc='convection-diffusion solver object')
-        self.options.declare('solver_NS', desc='NAVIER-STOKES solver object')
-        # not in the reference (whose components are forward-mode only): opt in to reverse mode
+    def _declare_adjoint(self):
         self.options.declare('adjoint', default=False, desc="also implement mode='rev' (adjoint derivatives)")
 
     def _rev(self, mode):
@@ -121,6 +119,15 @@ class ConvectionDiffusion_Component(_Base):
             return True
         _fwd_only(mode)
         return False
+
+
+class ConvectionDiffusion_Component(_AdjointOption):
+    """OpenMDAO/ConvectionDiffusion_Component.py:6-61: output T_cd, inputs u_ns, v_ns."""
+
+    def initialize(self):
+        self.options.declare('solver_CD', desc='convection-diffusion solver object')
+        self.options.declare('solver_NS', desc='NAVIER-STOKES solver object')
+        self._declare_adjoint()
 
     def setup(self):
         self.cd, self.ns = self.options['solver_CD'], self.options['solver_NS']
@@ -177,7 +184,7 @@ class ConvectionDiffusion_Component(_Base):
         self.iter_count_solve += 1
 
 
-class NavierStokes_Component(_Base):
+class NavierStokes_Component(_AdjointOption):
     """OpenMDAO/NavierStokes_Component.py:5-65: outputs u_ns, v_ns, p_ns, input T_cd."""
 
     _OUT = ('u_ns', 'v_ns', 'p_ns')
@@ -185,6 +192,7 @@ class NavierStokes_Component(_Base):
     def initialize(self):
         self.options.declare('solver_NS', desc='NAVIER-STOKES solver object')
         self.options.declare('solver_CD', desc='convection-diffusion solver object')
+        self._declare_adjoint()
 
     def setup(self):
         self.ns, self.cd = self.options['solver_NS'], self.options['solver_CD']
@@ -211,14 +219,33 @@ class NavierStokes_Component(_Base):
         self.ns._calc_jacobians(outputs['u_ns'], outputs['v_ns'])
 
     def apply_linear(self, inputs, outputs, d_inputs, d_outputs, d_residuals, mode, *args):
-        """(:42-50) forward mode only; absent d_outputs entries count as zero."""
-        _fwd_only(mode)
+        """(:42-50) forward mode; absent d_outputs entries count as zero.  With adjoint=True also mode='rev'
+        (accumulate into the entries that are present): for w = d_residuals[u_ns, v_ns, p_ns] (an absent entry
+        counts as zero) d_outputs[...] += A^T w and d_inputs['T_cd'] += change_inputs^T (dT_bar), the latter computed
+        only when T_cd is present."""
+        if self._rev(mode):
+            w = [np.asarray(d_residuals[n], dtype=np.float64) if n in d_residuals else np.zeros(self.ns.N)
+                 for n in self._OUT]
+            want_T = 'T_cd' in d_inputs
+            bars = self.ns._get_dresiduals_T(*w, want_T=want_T)
+            for n, a in zip(self._OUT, bars):
+                if n in d_outputs:
+                    d_outputs[n] += a
+            if want_T:
+                d_inputs['T_cd'] += transfer_T(bars[3], self.cd, self.ns)
+            return
         d = [d_outputs[n] if n in d_outputs else np.zeros(self.ns.N) for n in self._OUT]
         self._store(d_residuals, self.ns._get_dresiduals(*d, self.change_inputs(d_inputs['T_cd'])))
 
     def solve_linear(self, d_outputs, d_residuals, mode):
-        """(:52-60) the velocity-pressure update, current d_outputs as initial guesses."""
-        _fwd_only(mode)
+        """(:52-60) the velocity-pressure update, current d_outputs as initial guesses.  With adjoint=True also
+        mode='rev': d_residuals = the solution of A^T lambda = d_outputs, d_residuals['p_ns'] (when present) the
+        initial guess of the adjoint Schur solve."""
+        if self._rev(mode):
+            self._store(d_residuals, self.ns._get_update_T(
+                *(d_outputs[n] for n in self._OUT), dres_c0=d_residuals['p_ns'] if 'p_ns' in d_residuals else None))
+            self.iter_count_solve += 1
+            return
         self._store(d_outputs, self.ns._get_update(*(d_residuals[n] for n in self._OUT),
                                                    du0=d_outputs['u_ns'], dv0=d_outputs['v_ns'],
                                                    dp0=d_outputs['p_ns']))

@@ -103,6 +103,7 @@ class NavierStokesSolver:
         self._velocity_interior, self._velocity_graph = velocity_interior, velocity_graph
         self._velocity_sweep = velocity_sweep
         self._max_basis = max_basis
+        self._schur_maxiter = None   # cap of a whole-mesh Schur solve's iterations (None: the Krylov default, 10 N)
         self._velo = None
         self._Re, self._Gr = Re, Gr
         if self._Re == 0 and self._Gr != 0:
@@ -131,7 +132,7 @@ class NavierStokesSolver:
             self._C_x, self._C_y = ConvectionTensor(m, "x"), ConvectionTensor(m, "y")
         self._Sys = None
         self._Jac_u_u = self._Jac_u_v = self._Jac_v_u = self._Jac_v_v = None
-        self._jac_kw, self._schur = None, None
+        self._jac_kw, self._schur, self._schur_T = None, None, None
 
         # Dirichlet values and masks, exactly as NavierStokes_Solver.py:78-94 builds them
         x, y = self.points
@@ -255,7 +256,7 @@ class NavierStokesSolver:
         self._jac_kw = dict(self._sys_kw(self._Sys), juu=self._Jac_u_u._coeffs()[4], jvv=self._Jac_v_v._coeffs()[4],
                             juv=self._Jac_u_v._coeffs()[4], jvu=self._Jac_v_u._coeffs()[4])
         self._velo = None  # factorised on first use, reused until the next linearisation
-        self._schur = None
+        self._schur = self._schur_T = None
         if self._schur_recycle is not None:
             self._schur_recycle.reset()
 
@@ -504,6 +505,13 @@ class NavierStokesSolver:
         solve.  NumPy in, NumPy out; device tensors in, device tensors out.  Whole-mesh solvers whose factor is
         nested dissection only: there is no transposed line condensation and no transposed strip solve."""
         self._whole_mesh_only("velocity_solve_T")
+        xu, xv = self._velocity_solver_T().solve_T(self._dev(bu), self._dev(bv))
+        return self._out(xu, bu), self._out(xv, bu)
+
+    def _velocity_solver_T(self):
+        """_velocity_solver()'s factor made ready for transposed solves: the first call after a linearisation
+        registers _velocity_apply_lines_T, runs check_refinement_T and, with velocity_graph, captures the transposed
+        solve.  ValueError for a factor that is not nested dissection."""
         vs = self._velocity_solver()
         if not isinstance(vs, NestedDissectionSolver):
             raise ValueError("NavierStokes: velocity_solve_T needs the nested-dissection factor (P >= 2, the whole "
@@ -514,8 +522,7 @@ class NavierStokesSolver:
             vs.check_refinement_T()
             if self._velocity_graph:
                 vs.capture_T()
-        xu, xv = vs.solve_T(self._dev(bu), self._dev(bv))
-        return self._out(xu, bu), self._out(xv, bu)
+        return vs
 
     def _pressure_laplacian(self):
         """A_p = K with the pinned pressure row as an identity row (the Neumann pressure Laplacian
@@ -538,6 +545,14 @@ class NavierStokesSolver:
                                                                               "c_grady", "cv")},
                              c_extra=1.0, ea=c, eb=self._pcd_b)
         return self._pressure_laplacian().solve1(y)
+
+    def _mass_precond(self, c):
+        """The reference's Schur preconditioner (NavierStokes_Solver.py:207-212): the inverse mass diagonal, the
+        identity on the pinned row.  Diagonal, so it preconditions S and S^T alike."""
+        z = c / self._Mdiag
+        if self._pin >= 0:
+            z[self._pin] = c[self._pin]
+        return z
 
     def _get_update(self, dres_u, dres_v, dres_cont, du0=None, dv0=None, dp0=None):
         """Velocity solve + pressure Schur-complement Krylov solve (NavierStokes_Solver.py:162-236), on
@@ -567,16 +582,7 @@ class NavierStokesSolver:
             count[0] += 1
             return self._schur(dp)
 
-        pin = self._pin
-
-        def precon(c):
-            z = c / self._Mdiag
-            if pin >= 0:
-                z[pin] = c[pin]
-            return z
-
-        if self._schur_precond == "pcd":
-            precon = self._pcd
+        precon = self._pcd if self._schur_precond == "pcd" else self._mass_precond
 
         it = [0]
 
@@ -599,7 +605,8 @@ class NavierStokesSolver:
             cap = min(self.N, max(restart + 1, int(self._recycle_bytes // (16 * self.N))))
             self._schur_recycle = Recycle(self.N, torch.float64, self._mesh.device, cap)
         r = gcro(schur_mv, b_schur, x0=self._dev(dp0), atol=self._mtol * np.sqrt(self.N), rtol=0.0,
-                 restart=restart, precond=precon, callback=cb, recycle=self._schur_recycle)
+                 restart=restart, maxiter=self._schur_maxiter, precond=precon, callback=cb,
+                 recycle=self._schur_recycle)
         if r.info != 0:
             raise RuntimeError(f'NavierStokes LGMRES: Failed to converge in {r.info} iterations')
         dp = r.x
@@ -612,6 +619,77 @@ class NavierStokesSolver:
         m.ns_apply(None, None, dp, b_u, b_v, **self._ns_kw(pin_first=False))
         du, dv = vs.solve(ru - b_u, rv - b_v)
         return self._out(du, dres_u), self._out(dv, dres_u), self._out(dp, dres_u)
+
+    # ------------------------------------------------------------------ reverse mode (whole mesh)
+    def _get_dresiduals_T(self, ru_bar, rv_bar, rc_bar, want_T=False):
+        """Transpose of _get_dresiduals(du, dv, dp, dT): (du_bar, dv_bar, dp_bar) = A^T (ru_bar, rv_bar, rc_bar) for
+        the operator A of _get_dresiduals at dT = 0, and with want_T also dT_bar = -(Gr/Re) M (1 - m) rv_bar, so that
+        <_get_dresiduals(d), w> = <d, _get_dresiduals_T(w)> -- one fused launch (sem_ns_apply_transpose).  NumPy in,
+        NumPy out; device tensors in, device tensors out.  Needs _calc_jacobians, like the forward method."""
+        self._whole_mesh_only("_get_dresiduals_T")
+        if self._jac_kw is None:
+            raise RuntimeError("NavierStokes: _get_residuals and _calc_jacobians must run before _get_dresiduals_T")
+        m = self._mesh
+        zu, zv, zc = self._dev(ru_bar), self._dev(rv_bar), self._dev(rc_bar)
+        yu, yv, yp = (torch.empty_like(zu) for _ in range(3))
+        yT = torch.empty_like(zu) if want_T else None
+        m.ns_apply_transpose(zu, zv, zc, yu, yv, yp, yT, **self._jac_kw, c_T=-self._Gr_over_Re if want_T else 0.0,
+                             **self._ns_kw(pin_first=False))
+        out = (yu, yv, yp) + ((yT,) if want_T else ())
+        return tuple(self._out(y, ru_bar) for y in out)
+
+    def _get_update_T(self, du_bar, dv_bar, dp_bar, dres_c0=None):
+        """Adjoint of _get_update: (lam_u, lam_v, lam_c) with A^T lam = (du_bar, dv_bar, dp_bar), by the block
+        elimination of the forward update transposed:
+            f = J^-T [du_bar; dv_bar],   S^T q = dp_bar - B^T f,   [lam_u; lam_v] = J^-T ([du_bar; dv_bar] - C^T q),
+        lam_c = q, with S^T = E^T - B^T J^-T C^T (_SchurComplementT) solved by the device GMRES under the forward
+        update's mass-diagonal right preconditioner, stopping rule (||r||_2 <= mtol sqrt(N)) and restart; dres_c0 is
+        the initial guess of q.  No recycling.  Whole-mesh solvers with the nested-dissection factor and
+        schur_precond='mass' only: PCD's A_p^-T would need a transposed line condensation, which does not exist."""
+        self._whole_mesh_only("_get_update_T")
+        if self._schur_precond == "pcd":
+            raise ValueError("NavierStokes: _get_update_T needs schur_precond='mass': the PCD preconditioner's A_p^-T "
+                             "would need a transposed line condensation")
+        if self._jac_kw is None:
+            raise RuntimeError("NavierStokes: _get_residuals and _calc_jacobians must run before _get_update_T")
+        vs = self._velocity_solver_T()
+        m = self._mesh
+        kw = self._ns_kw(pin_first=False)
+        bu, bv, bp = self._dev(du_bar), self._dev(dv_bar), self._dev(dp_bar)
+        fu, fv = vs.solve_T(bu, bv)
+        c0 = torch.empty_like(bp)
+        m.ns_apply_transpose(fu, fv, None, yp=c0, **kw)    # B^T f
+        b_schur = bp - c0
+        if self._schur_T is None:
+            self._schur_T = _SchurComplementT(self, vs, graph=self._velocity_graph)
+        count = [0]
+
+        def schur_mv(q):
+            count[0] += 1
+            return self._schur_T(q)
+
+        it = [0]
+
+        def cb(est):
+            it[0] += 1
+            if 'LGMRES_iter' in self._iprint:
+                print(f'NavierStokes adjoint GMRES: {it[0]}\t{est}', flush=True)
+
+        restart = max(1, min(self.N, self._max_basis, int(32e9 // (16 * self.N))))   # _get_update's rule
+        r = gmres(schur_mv, b_schur, x0=self._dev(dres_c0), atol=self._mtol * np.sqrt(self.N), rtol=0.0,
+                  restart=restart, maxiter=self._schur_maxiter, precond=self._mass_precond, callback=cb)
+        if r.info != 0:
+            raise RuntimeError(f'NavierStokes adjoint GMRES: Failed to converge in {r.info} iterations')
+        q = r.x
+        self.schur_matvecs = count[0] - r.discarded     # dropped speculations are not counted
+        self.schur_discarded = r.discarded
+        if 'LGMRES_suc' in self._iprint:
+            res = (schur_mv(q) - b_schur).abs().max().item()
+            print(f'NavierStokes adjoint GMRES: Converged in {self.schur_matvecs} evaluations with max-norm {res}')
+        gu, gv = torch.empty_like(q), torch.empty_like(q)
+        m.ns_apply_transpose(None, None, q, gu, gv, c_div=-1.0, **kw)    # -C^T q
+        lu, lv = vs.solve_T(bu + gu, bv + gv)
+        return self._out(lu, du_bar), self._out(lv, du_bar), self._out(q, du_bar)
 
     def _get_solution(self, T, u0=None, v0=None, p0=None):
         """Newton iteration (NavierStokes_Solver.py:238-270), iterates kept on the device; NumPy in,
@@ -766,3 +844,20 @@ class _SchurComplement:
         self._x.copy_(dp)
         self._graph.replay()
         return self._out.clone()
+
+
+class _SchurComplementT(_SchurComplement):
+    """The adjoint Schur-complement operator of _get_update_T, S^T q = E^T q - B^T J^-T C^T q: the transposed-gradient
+    launch (-C^T q, written straight into the solve's [u | v] line buffer), the transposed velocity solve on the line
+    layout, and the transposed-divergence launch (B^T x + E^T q, reading the solution from it) -- two fused
+    sem_ns_apply_transpose launches around one solve, _SchurComplement._body mirrored, captured in one hipGraph per
+    linearisation by the same capture / fallback code."""
+
+    def _body(self, q):
+        ns, m, NY = self.ns, self.ns._mesh, self.ns._mesh.NY
+        B = self._B
+        m.ns_apply_transpose(None, None, q, B[:, :NY], B[:, NY:], c_div=-1.0, **ns._ns_kw(pin_first=False))
+        X = self.vs._solve_lines_T(B)
+        yp = torch.empty_like(q)
+        m.ns_apply_transpose(X[:, :NY], X[:, NY:], q, yp=yp, **ns._ns_kw(pin_first=False))
+        return yp
