@@ -393,6 +393,18 @@ int sem_nested_iface_rhs(const sem_nested_desc* d, const double* R, int64_t ld_r
  * condensed solve. */
 int sem_interface_rhs(int P, int nex, int m, const double* B, int64_t ld_b, const double* aBI, const double* yI,
                       int64_t ld_yI, double* g, void* stream);
+/* The transposed nested solve (entry point added at ABI 15; sem_amd/csrc/ns_condense_transpose.hip):
+ * Y = A_II^-T (R - A_BI^T x_B) for every element column from the SAME descriptor as sem_nested_solve -- no operator is
+ * stored transposed.  With S_e = A_ee - A_ei Xi A_ie:  C = Yie^T r_i (into d->C),  r_e -= C,  y_e = S_e^-T r_e by the
+ * transposed block-Thomas sweep w_k = r_k - Eu_{k-1}^T w_{k-1}, y_k = Ed_k^T (w_k - El_k^T y_{k+1}) (into d->Ye and Y),
+ * y_i = Xi^T (r_i - Aei^T [y_e(n); y_e(n+1)]).  R, ld_r, Y, ld_y as in sem_nested_solve; aBIt is aBI permuted into
+ * aIB's layout, aBIt[e][l-1][s][.] = aBI[e][s][l-1][.], and with xB gives r = R - aBIt[e][l-1][s][.] xB[e+s][.] (both
+ * NULL: no correction).  d->T is not used.  Three launches, stream-ordered; nothing is allocated (graph-capturable);
+ * the order of every sum is fixed by the shape and by the 16-byte alignment of Xi, Aei and Yie (bitwise repeatable).
+ * SEM_EUNSUPPORTED: d->Se != NULL (the dense edge inverse has no transposed kernel: the caller's torch path) and
+ * ne1 > 32; SEM_EINVAL: null pointers or bad sizes, before any launch.  SEM_TUNE_EDGE_THOMAS does not apply. */
+int sem_nested_solve_t(const sem_nested_desc* d, const double* R, int64_t ld_r, const double* aBIt, const double* xB,
+                       double* Y, int64_t ld_y, void* stream);
 
 /* ---- batched block GEMV (interface sweep of the velocity solve) ----------- */
 /* y[yrow[b]] (+)= sum_{s<S} M[b][:, s m:(s+1) m] . src[s][xrow[s nb + b]]  for b < nb (S <= 3):
@@ -405,6 +417,20 @@ int sem_interface_rhs(int P, int nex, int m, const double* B, int64_t ld_b, cons
  * rows, y, xrow and yrow are device memory.  Stream-ordered. */
 int sem_block_gemv(int nb, int m, int S, const double* M, const double* const* src, const int64_t* ld_src,
                    const int64_t* xrow, double* y, int64_t ld_y, const int64_t* yrow, int accumulate, void* stream);
+/* The transposed twin (entry point added at ABI 15): one level step of the transposed cyclic reduction, from the
+ * operators the forward sweep stores,
+ *   y[yrow[b]] (+)= sum_{s<S} M[mblk[s nb + b]][:, mcol[s] m : (mcol[s]+1) m]^T . src[s][xrow[s nb + b]]   b < nb, S <= 3.
+ * M: row-major blocks of m rows by W m columns (W <= 3: [alpha | gamma], [B^-1 | -B^-1 A | -B^-1 C] or one m x m
+ * block); mcol: host array of the S column slices (< W); mblk and xrow: device int64 (S, nb), -1 = that term is
+ * absent; src, ld_src, y, ld_y, yrow and `accumulate` as in sem_block_gemv.  Output rows must be distinct and not
+ * read by the same call.  form: 0 = by size (the wide form when ceil(m / 64) nb >= 256), 1 = wide (64 lanes along
+ * the columns, the rows split over the four waves), 2 = narrow (16 lanes, sixteen row groups: the coarsest levels'
+ * few blocks over four times the workgroups).  A lane sums its rows in increasing order into eight sums, the row
+ * groups meet in LDS in group order: no atomics, bitwise repeatable for a given form.  S m <= 8192
+ * (SEM_EUNSUPPORTED above; the caller's batched product).  Stream-ordered, nothing allocated. */
+int sem_block_gemv_t(int nb, int m, int S, int W, const double* M, const int* mcol, const int64_t* mblk,
+                     const double* const* src, const int64_t* ld_src, const int64_t* xrow, double* y, int64_t ld_y,
+                     const int64_t* yrow, int accumulate, int form, void* stream);
 
 /* ---- streaming row-major GEMV (the block-Thomas interface sweep) -------- */
 /* y = alpha A x + beta y (beta = 0: y is not read) for a row-major M x K operator (row i at A + i lda):
@@ -487,8 +513,10 @@ int sem_leaf_forward(const sem_leaf_launch* d, void* stream);
 
 /* ---- transposed nested-dissection solve J^T x = b (entry points added at ABI 15) ---- */
 /* The steps of NestedDissectionSolver.solve_T: the same stored operators as the forward solve, streamed the other
- * way (no transposed copies).  What exists: the velocity factor's transposed solve.  What does not: a transposed
- * Schur solve, strips, a transposed line condensation.
+ * way (no transposed copies).  What exists: the velocity factor's transposed solve, and the
+ * transposed line condensation (sem_nested_solve_t, sem_block_gemv_t above: the nested interior on the block-Thomas
+ * edge form and the cyclic-reduction sweep).  What does not: a transposed Schur solve, strips, transposed twins of
+ * the ABI-11 coupled forms, HIP for the transposed block-Thomas interface sweeps and the dense edge inverse.
  * sem_front_gemv_t: one launch = one level of y_f = A_f^T x_f.  Item f has a ROW-MAJOR operator at op[f] (device
  * address, 16-byte aligned; dims[4 f .. 4 f + 2] = R_f operand rows, K_f output columns, leading dimension ld_f;
  * K_f and ld_f even, K_f <= ld_f), its R_f operand positions in W at xidx[xoff[f] ..] (-1: a zero operand) and

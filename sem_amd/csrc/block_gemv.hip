@@ -13,6 +13,7 @@
 // are rows the launch does not write (the caller's level structure guarantees it).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 
 #include "sem_internal.h"
@@ -106,6 +107,81 @@ __global__ __launch_bounds__(64 * kGemvWaves) void block_gemv_narrow_kernel(cons
   if (lane == 0) {
     double* yb = a.y + a.yrow[b] * a.ld_y;
     yb[r] = a.accumulate ? yb[r] + v : v;
+  }
+}
+
+// ---- Transposed block GEMV with gathered operands: the level step of the TRANSPOSED cyclic reduction
+// (VelocityJacobianSolver._cr_solve_T), from the operators the forward sweep stores:
+//
+//   y[yrow[b]] (+)= sum_{s < S} M[mblk[s][b]][:, mcol[s] m : (mcol[s]+1) m]^T . src_s[xrow[s][b]]      b = 0 .. nb-1
+//
+// M holds row-major blocks of m rows by W m columns; term s reads the m x m column slice mcol[s] of block
+// mblk[s][b], transposed: output column c sums M[r][mcol[s] m + c] x_s[r] over the rows r.  Lanes run along the
+// contiguous columns (one column per lane: m is odd for one component, so the loads are 8 bytes wide), the rows are
+// split over the 256 / LANES row groups of the workgroup (LANES = 64: the four waves), every lane keeps kGemvTUnroll
+// independent sums (that many loads in flight), and the groups' sums meet in LDS in group order: no atomics, bitwise
+// repeatable for a given LANES.  The S operand rows are staged in LDS, which then holds the groups' sums.
+// Wide form: LANES = 64, grid (ceil(m / 64), nb).  Narrow form (the coarsest levels, a few blocks): LANES = 16, so one
+// block's columns spread over four times as many workgroups and its rows over sixteen groups of each.
+constexpr int kGemvTThreads = 256;
+constexpr int kGemvTUnroll = 8;
+
+struct GemvTArgs {
+  const double* M;
+  const double* src[3];
+  const int64_t* mblk;  // (S, nb); -1: no such term
+  const int64_t* xrow;  // (S, nb); -1: no such term
+  const int64_t* yrow;  // (nb)
+  double* y;
+  int64_t ld_src[3], ld_y;
+  int nb, m, S, W, mcol[3], accumulate;
+};
+
+template <int LANES>
+__global__ __launch_bounds__(kGemvTThreads) void block_gemv_t_kernel(const GemvTArgs a) {
+  extern __shared__ double xs[];  // max(S m, 256): the gathered operand rows, then the row groups' sums
+  constexpr int G = kGemvTThreads / LANES, U = kGemvTUnroll;
+  const int b = blockIdx.y, m = a.m;
+  for (int s = 0; s < a.S; ++s) {
+    const int64_t r = a.xrow[static_cast<int64_t>(s) * a.nb + b], blk = a.mblk[static_cast<int64_t>(s) * a.nb + b];
+    const double* src = (r >= 0 && blk >= 0) ? a.src[s] + r * a.ld_src[s] : nullptr;
+    for (int j = threadIdx.x; j < m; j += blockDim.x) xs[s * m + j] = src ? src[j] : 0.0;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x % LANES, grp = threadIdx.x / LANES;
+  const int c = blockIdx.x * LANES + lane, cc = min(c, m - 1);  // clamped columns are computed, not stored
+  const int rb = static_cast<int>(static_cast<int64_t>(m) * grp / G);
+  const int re = static_cast<int>(static_cast<int64_t>(m) * (grp + 1) / G);
+  const int64_t ld = static_cast<int64_t>(a.W) * m;
+  double acc[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) acc[u] = 0.0;
+  for (int s = 0; s < a.S; ++s) {  // absent terms are skipped by the whole workgroup
+    const int64_t blk = a.mblk[static_cast<int64_t>(s) * a.nb + b];
+    if (blk < 0 || a.xrow[static_cast<int64_t>(s) * a.nb + b] < 0) continue;
+    const double* Ms = a.M + blk * m * ld + static_cast<int64_t>(a.mcol[s]) * m + cc;
+    const double* x = xs + s * m;
+    int r = rb;
+    for (; r + U <= re; r += U) {
+      double v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[u] = Ms[(r + u) * ld];
+#pragma unroll
+      for (int u = 0; u < U; ++u) acc[u] = fma(v[u], x[r + u], acc[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U - 1; ++u)
+      if (r + u < re) acc[u] = fma(Ms[(r + u) * ld], x[r + u], acc[u]);
+  }
+  const double v = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+  __syncthreads();  // every group is done with the operands
+  xs[grp * LANES + lane] = v;
+  __syncthreads();
+  if (grp == 0 && c < m) {
+    double sum = xs[lane];
+    for (int g = 1; g < G; ++g) sum += xs[g * LANES + lane];
+    double* yb = a.y + a.yrow[b] * a.ld_y;
+    yb[c] = a.accumulate ? yb[c] + sum : sum;
   }
 }
 
@@ -321,6 +397,49 @@ int sem_block_gemv(int nb, int m, int S, const double* M, const double* const* s
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return sem::set_error(SEM_EHIP, std::string("block_gemv launch: ") + hipGetErrorString(e));
+  return SEM_OK;
+}
+
+int sem_block_gemv_t(int nb, int m, int S, int W, const double* M, const int* mcol, const int64_t* mblk,
+                     const double* const* src, const int64_t* ld_src, const int64_t* xrow, double* y, int64_t ld_y,
+                     const int64_t* yrow, int accumulate, int form, void* stream) {
+  static_assert(sem::kGemvTUnroll == 8, "block_gemv_t_kernel combines eight sums");
+  if (nb < 0 || m < 1 || S < 1 || S > 3 || W < 1 || W > 3 || form < 0 || form > 2)
+    return sem::set_error(SEM_EINVAL, "block_gemv_t: bad sizes");
+  if (!M || !mcol || !mblk || !src || !ld_src || !xrow || !y || !yrow)
+    return sem::set_error(SEM_EINVAL, "block_gemv_t: null argument");
+  sem::GemvTArgs a{};
+  for (int s = 0; s < S; ++s) {
+    if (!src[s]) return sem::set_error(SEM_EINVAL, "block_gemv_t: null operand");
+    if (mcol[s] < 0 || mcol[s] >= W) return sem::set_error(SEM_EINVAL, "block_gemv_t: column slice outside the block");
+    a.src[s] = src[s];
+    a.ld_src[s] = ld_src[s];
+    a.mcol[s] = mcol[s];
+  }
+  if (static_cast<int64_t>(S) * m > 8192) return sem::set_error(SEM_EUNSUPPORTED, "block_gemv_t: S m above 8192 doubles");
+  if (nb == 0) return SEM_OK;
+  a.M = M;
+  a.mblk = mblk;
+  a.xrow = xrow;
+  a.yrow = yrow;
+  a.y = y;
+  a.ld_y = ld_y;
+  a.nb = nb;
+  a.m = m;
+  a.S = S;
+  a.W = W;
+  a.accumulate = accumulate;
+  const size_t lds = static_cast<size_t>(std::max(S * m, sem::kGemvTThreads)) * sizeof(double);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // form 0: the wide form where its 64-column workgroups fill the chip's 256 CUs, the narrow form below that
+  const int wide_blocks = (m + 63) / 64;
+  const bool wide = form == 1 || (form == 0 && static_cast<int64_t>(wide_blocks) * nb >= 256);
+  if (wide)
+    hipLaunchKernelGGL(sem::block_gemv_t_kernel<64>, dim3(wide_blocks, nb), dim3(sem::kGemvTThreads), lds, s, a);
+  else
+    hipLaunchKernelGGL(sem::block_gemv_t_kernel<16>, dim3((m + 15) / 16, nb), dim3(sem::kGemvTThreads), lds, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return sem::set_error(SEM_EHIP, std::string("block_gemv_t launch: ") + hipGetErrorString(e));
   return SEM_OK;
 }
 

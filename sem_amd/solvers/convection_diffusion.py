@@ -242,8 +242,11 @@ class ConvectionDiffusionSolver:
     def _get_update_T(self, dT_bar, dres0=None):
         """Adjoint of the Newton update: solve A_D^T lambda = dT_bar with the device GMRES, every
         iteration one fused transposed apply.  Stopping rule and restart are the forward solve's
-        (atol = mtol sqrt(N), rtol = 0, restart = min(int(0.3 N), max_basis)).  Unpreconditioned: the
-        condensed direct factor solves with A_D, not with its transpose."""
+        (atol = mtol sqrt(N), rtol = 0, restart = min(int(0.3 N), max_basis)).  With precond="condensed"
+        (the default) it is right-preconditioned, as the forward solve is, by the condensed direct factor
+        applied transposed (VelocityJacobianSolver.solve1_T: the same factor, no second one; restart at most
+        100; on the GPU the transposed solve is captured in a graph on its first use); the stopping test stays
+        on the true residual.  precond=None: the unpreconditioned solve."""
         self._whole_mesh_only("_get_update_T")
         if self._Sys is None:
             raise RuntimeError("ConvectionDiffusion: _get_residuals must run before _get_update_T")
@@ -257,8 +260,15 @@ class ConvectionDiffusionSolver:
                 print(f"ConvectionDiffusion adjoint GMRES: {it[0]}\t{est}", flush=True)
 
         restart = max(1, min(int(self.N * 0.3), self._max_basis))
+        kw = {}
+        if self._precond == "condensed":
+            vs = self._jacobian_solver()
+            if vs.device.type == "cuda" and vs._graph_T is None:
+                vs.capture_T()
+            kw = dict(precond=vs.solve1_T)
+            restart = min(restart, 100)
         r = gmres(lambda v: self._apply_T(v), b, x0=x0, atol=self._mtol * np.sqrt(self.N), rtol=0.0, restart=restart,
-                  maxiter=10 * self.N, callback=cb)
+                  maxiter=10 * self.N, callback=cb, **kw)
         if r.info != 0:
             raise RuntimeError(f"ConvectionDiffusion LGMRES: Failed to converge in {r.info} iterations")
         self.matvecs = r.matvecs
@@ -290,7 +300,9 @@ class ConvectionDiffusionSolver:
                 vs = StripLineSolver(self._P, self._N_ex, self._N_ey, m.device, p.part.bounds, p.rank, p.dist,
                                      group=p.group, ncomp=1, gather_device=p.backend_device())
             else:
-                vs = VelocityJacobianSolver(self._P, self._N_ex, self._N_ey, m.device, ncomp=1)
+                # transpose=True: the same factor preconditions the adjoint solve (_get_update_T); nothing of the
+                # forward solve changes, and what the transposed solve adds is built on its first use
+                vs = VelocityJacobianSolver(self._P, self._N_ex, self._N_ey, m.device, ncomp=1, transpose=True)
             cX, cu, cY, cv, d = self._Sys._coeffs()
             vs.factor_mesh(m, c_mass=self._Sys.cM, c_stiff=self._Sys.cK, c_gradx=cX, cu=cu, c_grady=cY, cv=cv, juu=d,
                            **self._dir.kw())

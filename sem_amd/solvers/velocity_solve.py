@@ -362,11 +362,76 @@ def fused_thomas_solve(D0, F, Uh, g):
     return z.contiguous()             # sem_nested_solve reads x_B as a packed (n, m) array
 
 
+# ---- transposed interface sweeps: x = S^-T b from the forward sweeps' stored operators.  Every forward sweep is a
+# list of steps y (+)= alpha A x; its transpose is the same list backwards, each step x_bar += alpha A^T y_bar
+# (torch products with .mT: the Thomas forms have no transposed HIP kernel and are not tuned).  b is not modified.
+
+def plain_thomas_solve_T(Dinv, S_lo, Uh, b):
+    """x = S^-T b from the plain block-Thomas factors (the transpose of _iface_solve's last form)."""
+    n = b.shape[0]
+    z = b.clone()
+    for L in range(n - 1):                       # the back substitution x_L -= Uh_L x_{L+1}, reversed
+        z[L + 1] -= Uh[L].mT @ z[L]
+    g = torch.empty_like(b)
+    for L in range(n - 1, 0, -1):                # z_L = Dinv_L (g_L - S_lo[L-1] z_{L-1}), reversed
+        g[L] = Dinv[L].mT @ z[L]
+        z[L - 1] -= S_lo[L - 1].mT @ g[L]
+    g[0] = Dinv[0].mT @ z[0]
+    return g
+
+
+def fused_thomas_solve_T(D0, F, Uh, b):
+    """x = S^-T b from fused_thomas_operators (the transpose of fused_thomas_solve)."""
+    n, m = b.shape[0], b.shape[1]
+    z = b.clone()
+    for L in range(n - 1):
+        z[L + 1] -= Uh[L].mT @ z[L]
+    g = torch.empty_like(b)
+    for L in range(n - 1, 0, -1):                # z_L = F_{L-1} [g_L; z_{L-1}], reversed
+        v = F[L - 1].mT @ z[L]
+        g[L] = v[:m]
+        z[L - 1] += v[m:]
+    g[0] = D0.mT @ z[0]
+    return g
+
+
+def twisted_thomas_solve_T(op, b):
+    """x = S^-T b from twisted_thomas_operators (the transpose of twisted_thomas_solve): the two back chains
+    reversed (they meet at line k), the middle step, then the two forward chains reversed."""
+    k, D0, E0, FT, FB, FM, UhT, UhB = op
+    n, m = b.shape[0], b.shape[1]
+    z = b.clone()
+    for L in range(n - 1, k, -1):                # x_L = w_L - UhB_L x_{L-1}, reversed
+        z[L - 1] -= UhB[L - (k + 1)].mT @ z[L]
+    for L in range(k):                           # x_L = z_L - UhT_L x_{L+1}, reversed
+        z[L + 1] -= UhT[L].mT @ z[L]
+    g = torch.empty_like(b)
+    v = FM.mT @ z[k]                             # x_k = FM [g_k; z_{k-1}; w_{k+1}]
+    g[k] = v[:m]
+    z[k - 1] += v[m:2 * m]
+    z[k + 1] += v[2 * m:]
+    for L in range(k - 1, 0, -1):
+        v = FT[L - 1].mT @ z[L]
+        g[L] = v[:m]
+        z[L - 1] += v[m:]
+    g[0] = D0.mT @ z[0]
+    for L in range(k + 1, n - 1):
+        v = FB[L - (k + 1)].mT @ z[L]
+        g[L] = v[:m]
+        z[L + 1] += v[m:]
+    g[n - 1] = E0.mT @ z[n - 1]
+    return g
+
+
 class VelocityJacobianSolver:
     """x = J^-1 b for the velocity Jacobian J of one linearisation, J given by its condensation pieces."""
 
-    def __init__(self, P, nex, ney, device, interior="nested", sweep="auto", ncomp=2):
-        """ncomp: unknowns per node -- 2 for the velocity pair [u | v], 1 for a scalar operator
+    def __init__(self, P, nex, ney, device, interior="nested", sweep="auto", ncomp=2, transpose=False):
+        """transpose: the factor also serves J^T x = b (solve_T, solve1_T, _solve_lines_T, check_refinement_T,
+        capture_T) from the operators it stores for the forward solve -- the nested interior only; what the
+        transposed solve needs beyond them (two permuted copies of the line couplings, index tables) is built on
+        its first use.  The forward factor and its solves are the same with or without it.
+        ncomp: unknowns per node -- 2 for the velocity pair [u | v], 1 for a scalar operator
         (the convection-diffusion Jacobian, or the pressure stiffness of the Schur preconditioner).
         interior: elimination of the element-column interiors ("nested" static condensation, or
         one dense block per column: "lu" factors, "inverse" explicit inverses).  sweep: solve of the
@@ -383,6 +448,15 @@ class VelocityJacobianSolver:
             raise ValueError("sweep must be 'cr', 'thomas' or 'auto'")
         if ncomp not in (1, 2):
             raise ValueError("ncomp must be 1 or 2")
+        if transpose and interior != "nested":
+            raise NotImplementedError("the transposed line condensation needs interior='nested' (the dense column "
+                                      "interiors keep A_II^-1 A_IB, not what its transpose needs)")
+        self.transpose = bool(transpose)
+        # transposed solve: tables built on its first use (_transpose_tables); refine_T is check_refinement_T's gate
+        self._aIBp = self._aBIp = self._cr_T = self._graph_T = None
+        self._apply_T = None
+        self.refine_T = False
+        self.refine_eta_T = None
         self.sweep, self.ncomp = sweep, ncomp
         self.P, self.nex, self.ney = P, nex, ney
         self.NY, self.NX = ney * P + 1, nex * P + 1
@@ -824,6 +898,7 @@ class VelocityJacobianSolver:
 
     def _sweep_factor(self, S_diag, S_up, S_lo):
         nex, m = self.nex, self.m
+        self._aIBp = self._aBIp = self._cr_T = self._graph_T = None   # a new factor: the transposed tables are stale
         if self.sweep == "cr":
             self._cr_factor(S_diag, S_up, S_lo)
             self.factored = True
@@ -962,6 +1037,85 @@ class VelocityJacobianSolver:
             gemv(back, (g, x, x), bx, x, elim, False)
         return x
 
+    # ------------------------------------------------------------------ cyclic reduction, transposed
+    # x = S^-T b from the levels _cr_factor stored.  The forward solve is Back_1 .. Back_L Top Fwd_L .. Fwd_1 (1: the
+    # finest level), so its transpose runs Back_1^T .. Back_L^T, Top^T, Fwd_L^T .. Fwd_1^T on x_bar = b, g_bar = 0:
+    #   fine -> coarse   g_bar[elim_j]  = back_j[:, 0:m]^T x_bar[elim_j]
+    #                    x_bar[keep_i] += back_{right_i}[:, m:2m]^T x_bar[right_i] + back_{left_i}[:, 2m:3m]^T x_bar[left_i]
+    #   top              g_bar[top]     = Tinv^T x_bar[top]
+    #   coarse -> fine   g_bar[elim_j] += gamma_{keep_j}^T g_bar[keep_j] + alpha_{br_j}^T g_bar[br_j]
+    # and x = g_bar.  Every step gathers: its targets are distinct and no operand of the same step, each m x m slice
+    # of a stored operator is read once per solve (the forward solve's bytes), and nothing is stored transposed.
+    def _cr_tables_T(self):
+        """Block and row tables of the transposed levels (built once per factor): per level
+        (elim, keep, e_blocks, (mblk, xrow) of the x_bar update, (mblk, xrow) of the g_bar update)."""
+        if self._cr_T is None:
+            dev = self.device
+            out = []
+            for keep, _, _, elim, _, _, lr, bx in self._cr:
+                k, e = keep.numel(), elim.numel()
+                i = torch.arange(k, device=dev)
+                posr = torch.where(i < e, i, torch.full_like(i, -1))          # right_i = elim[i]
+                posl = i - 1                                                  # left_i = elim[i - 1]; -1 at i = 0
+                j = torch.arange(e, device=dev)
+                nxt = torch.where(j + 1 < k, j + 1, torch.full_like(j, -1))   # br_j = keep[j + 1]
+                out.append((elim, keep, j.reshape(1, -1).contiguous(), elim.reshape(1, -1).contiguous(),
+                            torch.stack((posr, posl)).contiguous(), torch.stack((lr[1], lr[0])).contiguous(),
+                            torch.stack((j, nxt)).contiguous(), torch.stack((bx[1], bx[2])).contiguous()))
+            top = self._cr_top[0]
+            t = torch.arange(top.numel(), device=dev).reshape(1, -1).contiguous()
+            self._cr_T = (out, t, top.reshape(1, -1).contiguous())
+        return self._cr_T
+
+    def _block_gemv_T(self, M, W, mcol, mblk, srcs, xrow, y, yrow, acc):
+        """y[yrow[b]] (+)= sum_s M[mblk[s][b]][:, mcol[s] m:(mcol[s]+1) m]^T srcs[s][xrow[s][b]] (-1: absent): one
+        sem_block_gemv_t launch on the GPU; batched torch products on the CPU and for operands beyond the kernel's
+        LDS staging."""
+        m, S = y.shape[1], len(srcs)
+        if y.is_cuda and S * m <= GEMV_LDS_DOUBLES and getattr(self, "hip_nested", True):
+            import ctypes as C
+            from .. import _lib
+            if not (M.is_contiguous() and xrow.is_contiguous() and yrow.is_contiguous() and mblk.is_contiguous()
+                    and xrow.dtype == yrow.dtype == mblk.dtype == torch.int64 and tuple(M.shape[1:]) == (m, W * m)
+                    and tuple(xrow.shape) == tuple(mblk.shape) == (S, yrow.numel())):
+                raise ValueError("sem_block_gemv_t: operator / index layout")
+            lib = _lib.load()
+            P = C.c_void_p
+            stream = P(torch.cuda.current_stream(self.device).cuda_stream)
+            src = (P * S)(*(P(t.data_ptr()) for t in srcs))
+            ld = (C.c_int64 * S)(*(t.stride(0) for t in srcs))
+            mc = (C.c_int * S)(*mcol)
+            _lib.check(lib.sem_block_gemv_t(yrow.numel(), m, S, W, P(M.data_ptr()), mc, P(mblk.data_ptr()),
+                                            src, ld, P(xrow.data_ptr()), P(y.data_ptr()), y.stride(0),
+                                            P(yrow.data_ptr()), int(acc), getattr(self, "gemv_t_form", 0), stream))
+            return
+        out = None
+        for s in range(S):
+            ok = ((mblk[s] >= 0) & (xrow[s] >= 0))[:, None]
+            A = M[mblk[s].clamp(min=0)][:, :, mcol[s] * m:(mcol[s] + 1) * m]
+            v = torch.where(ok, srcs[s][xrow[s].clamp(min=0)], 0.0)
+            t = torch.bmm(A.mT, v[..., None])[..., 0]
+            out = t if out is None else out + t
+        if acc:
+            y[yrow] += out
+        else:
+            y[yrow] = out
+
+    def _cr_solve_T(self, b):
+        """x = S^-T b for the interface system from the cyclic-reduction levels; b (N_ex + 1, m) is not modified."""
+        levels, tblk, trow = self._cr_tables_T()
+        xb, g = b.clone(), torch.zeros_like(b)
+        gemv = self._block_gemv_T
+        for (elim, keep, eb, er, mb2, xr2, _, _), lev in zip(levels, self._cr):
+            back = lev[4]
+            gemv(back, 3, (0,), eb, (xb,), er, g, elim, False)
+            gemv(back, 3, (1, 2), mb2, (xb, xb), xr2, xb, keep, True)
+        top, Tinv = self._cr_top
+        gemv(Tinv, 1, (0,), tblk, (xb,), trow, g, top, False)
+        for (elim, keep, _, _, _, _, mb3, xr3), lev in zip(reversed(levels), reversed(self._cr)):
+            gemv(lev[1], 2, (1, 0), mb3, (g, g), xr3, g, elim, True)
+        return g
+
     # ------------------------------------------------------------------ nested interior (default)
     # Inside one element column the interior unknowns split again: the interiors of its elements
     # (y nodes strictly inside element n, on all P-1 interior lines: 2 (P-1)^2 unknowns) couple only
@@ -1028,6 +1182,43 @@ class VelocityJacobianSolver:
         for k in range(nb - 2, -1, -1):
             Z[:, k] -= Eu[:, k] @ Z[:, k + 1]
         return Z.view(Re.shape)
+
+    def _nested_solve_T(self, R, cols=slice(None)):
+        """A_II^-T R for every column (or the columns `cols`) from the forward factor; R (columns, nI, k).  With
+        S_e = A_ee - A_ei Xi A_ie:  r_e -= Yie^T r_i,  y_e = S_e^-T r_e,  y_i = Xi^T (r_i - A_ei^T [y_e(n); y_e(n+1)])."""
+        nex, ney, ne1 = R.shape[0], self.ney, self._ne1
+        k = R.shape[-1]
+        Ri = R[:, self._pi]                                             # (nex, ney, ni, k)
+        Re = R[:, self._pe].clone()                                     # (nex, n_e, k)
+        Cn = self._Yie[cols].mT @ Ri                                    # (nex, ney, 2 ne1, k)
+        Rv = Re.view(nex, ney + 1, ne1, k)
+        Rv[:, :-1] -= Cn[:, :, :ne1]
+        Rv[:, 1:] -= Cn[:, :, ne1:]
+        if self._edge_thomas:
+            Ye = self._edge_thomas_solve_T(Re, cols)
+        else:
+            Ye = self._Se_inv[cols].mT @ Re                             # (nex, n_e, k)
+        Yv = Ye.view(nex, ney + 1, ne1, k)
+        Yi = self._Xi[cols].mT @ (Ri - self._Aei[cols].mT @ torch.cat((Yv[:, :-1], Yv[:, 1:]), dim=2))
+        Y = torch.empty_like(R)
+        Y[:, self._pi] = Yi
+        Y[:, self._pe] = Ye
+        return Y
+
+    def _edge_thomas_solve_T(self, Re, cols=slice(None)):
+        """S_e^-T Re from the block-Thomas factors (the torch form of cond_edge_thomas_t_kernel):
+        w_k = r_k - Eu_{k-1}^T w_{k-1},  then  y_k = Ed_k^T (w_k - El_k^T y_{k+1})."""
+        Ed, El, Eu = self._Ed[cols], self._El[cols], self._Eu[cols]
+        nex, nb, b = Ed.shape[0], Ed.shape[1], Ed.shape[2]
+        R = Re.view(nex, nb, b, -1)
+        Y = torch.empty_like(R)
+        Y[:, 0] = R[:, 0]
+        for k in range(1, nb):
+            Y[:, k] = R[:, k] - Eu[:, k - 1].mT @ Y[:, k - 1]
+        Y[:, nb - 1] = Ed[:, nb - 1].mT @ Y[:, nb - 1]
+        for k in range(nb - 2, -1, -1):
+            Y[:, k] = Ed[:, k].mT @ (Y[:, k] - El[:, k].mT @ Y[:, k + 1])
+        return Y.view(Re.shape)
 
     # ------------------------------------------------------------------ solve
     def _hip_nested(self):
@@ -1118,10 +1309,12 @@ class VelocityJacobianSolver:
         return out
 
     # ------------------------------------------------------------------ iterative refinement
-    def set_operator(self, apply_lines, amax=None):
+    def set_operator(self, apply_lines, amax=None, apply_lines_T=None):
         """apply_lines(X) -> J X on (NX, m) line arrays (the matrix-free Jacobian apply of the solver that owns
-        this factor); amax(t) -> max |t| over every part (a partitioned solve reduces over the ranks)."""
+        this factor); amax(t) -> max |t| over every part (a partitioned solve reduces over the ranks);
+        apply_lines_T(X) -> J^T X is the operator of check_refinement_T and of the transposed solve's refinement."""
         self._apply = apply_lines
+        self._apply_T = apply_lines_T
         self._amax = amax if amax is not None else (lambda t: float(t.abs().max()))
 
     def check_refinement(self, tau=None, seed=17):
@@ -1207,6 +1400,153 @@ class VelocityJacobianSolver:
             out[:-1].view(nex, P, m)[:, 1:, :] = xI.view(nex, P - 1, m)
         return out
 
+    # ------------------------------------------------------------------ transposed solve (transpose=True)
+    # J^T x = b from the forward factor.  With the lines split into column interiors I and interface lines B,
+    #     y_I = A_II^-T b_I,   g = b_B - A_IB^T y_I,   S^T x_B = g,   x_I = A_II^-T (b_I - A_BI^T x_B):
+    # the forward solve's four steps with aIB and aBI in each other's place and every stored operator applied
+    # transposed.  A_IB and A_BI are diagonal per line, so the only transposed data kept are the two permuted copies
+    # of those diagonals (2 (P-1) m doubles per column each), in each other's layout.
+    def _require_T(self):
+        if not self.transpose:
+            raise NotImplementedError("the line-condensation velocity solve serves no transposed solve unless it is "
+                                      "built with transpose=True (the transposed condensation, nested interior); "
+                                      "NestedDissectionSolver has solve_T as well")
+        if not self.factored:
+            raise RuntimeError("factor() first")
+        if self.P > 1 and self._aIBp is None:
+            self._aIBp = self.aIB.permute(0, 2, 1, 3).contiguous()      # aIB in aBI's layout: [e, s, l, r]
+            self._aBIp = self.aBI.permute(0, 2, 1, 3).contiguous()      # aBI in aIB's layout: [e, l, s, r]
+
+    def _iface_solve_T(self, g):
+        """The transposed interface system S^T x_B = g (g is not modified)."""
+        if self.sweep == "cr":
+            return self._cr_solve_T(g)
+        if getattr(self, "_tw", None) is not None:
+            return twisted_thomas_solve_T(self._tw, g)
+        if getattr(self, "_th", None) is not None:
+            return fused_thomas_solve_T(*self._th, g)
+        return plain_thomas_solve_T(self.Dinv, self.S_lo, self.Uh, g)
+
+    def _solve_lines_hip_T(self, B):
+        """_solve_lines_once_T on the GPU: sem_nested_solve_t (ns_condense_transpose.hip), sem_interface_rhs with
+        the permuted aIB, the transposed interface sweep, sem_nested_solve_t with the permuted aBI and x_B.  The
+        "full" path of the forward solve (two nested solves through Xi); the work arrays are the forward solve's."""
+        import ctypes as C
+        from .. import _lib
+        lib = _lib.load()
+        P, nex, m, NX = self.P, self.nex, self.m, self.NX
+        if not (B.is_contiguous() and tuple(B.shape) == (NX, m) and B.dtype == torch.float64):
+            raise ValueError("line array must be a contiguous float64 (NX, m) tensor")
+        d = self._hip_nested()
+        _, _, _, yI, g, _ = self._work
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        v = C.c_void_p
+        b1 = B.data_ptr() + 8 * m   # line e P + 1: first interior line of column e
+        with phase("vsolve_T.nested_fwd"):
+            _lib.check(lib.sem_nested_solve_t(C.byref(d), v(b1), P * m, None, None, v(yI.data_ptr()), self.nI, st))
+            _lib.check(lib.sem_interface_rhs(P, nex, m, v(B.data_ptr()), m, v(self._aIBp.data_ptr()),
+                                             v(yI.data_ptr()), self.nI, v(g.data_ptr()), st))
+        with phase("vsolve_T.iface_solve"):
+            xB = self._iface_solve_T(g)
+        out = torch.empty((NX, m), dtype=torch.float64, device=self.device)
+        out[0::P] = xB
+        with phase("vsolve_T.nested_back"):
+            _lib.check(lib.sem_nested_solve_t(C.byref(d), v(b1), P * m, v(self._aBIp.data_ptr()), v(xB.data_ptr()),
+                                              v(out.data_ptr() + 8 * m), P * m, st))
+        return out
+
+    def _solve_lines_once_T(self, B):
+        self._require_T()
+        P, nex, m, NX = self.P, self.nex, self.m, self.NX
+        if (self.device.type == "cuda" and P > 1 and self._edge_thomas and self._ne1 <= 32
+                and getattr(self, "hip_nested", True)):
+            return self._solve_lines_hip_T(B)   # (a factor on the dense edge inverse takes the torch path below)
+        g = B[0::P].clone()                                    # interface lines (nex+1, m)
+        if P > 1:
+            bI = B[:-1].reshape(nex, P, m)[:, 1:, :].reshape(nex, self.nI, 1)
+            yIr = self._nested_solve_T(bI).view(nex, P - 1, m)
+            g[:-1] -= (self.aIB[:, :, 0] * yIr).sum(1)
+            g[1:] -= (self.aIB[:, :, 1] * yIr).sum(1)
+        xB = self._iface_solve_T(g)
+        out = torch.empty((NX, m), dtype=torch.float64, device=self.device)
+        out[0::P] = xB
+        if P > 1:   # x_I = A_II^-T (b_I - A_BI^T x_B); A_BI is diagonal per line
+            rI = bI.view(nex, P - 1, m) - (self.aBI[:, 0] * xB[:-1, None, :] + self.aBI[:, 1] * xB[1:, None, :])
+            xI = self._nested_solve_T(rI.reshape(nex, self.nI, 1))
+            out[:-1].view(nex, P, m)[:, 1:, :] = xI.view(nex, P - 1, m)
+        return out
+
+    def _solve_lines_T(self, B):
+        """x = J^-T b with b, x as (NX, ncomp NY) line arrays; with `refine_T` set, one step of iterative refinement
+        on the transposed matrix-free apply (set_operator's apply_lines_T)."""
+        X = self._solve_lines_once_T(B)
+        if self.refine_T:
+            if self._apply_T is None:
+                raise RuntimeError("refine_T is set but no transposed operator: set_operator(..., apply_lines_T=...)")
+            X = X + self._solve_lines_once_T(B - self._apply_T(X))
+        return X
+
+    def check_refinement_T(self, tau=None, seed=17):
+        """check_refinement for the transposed solve: eta = ||J^T x - b|| / (||J^T|| ||x|| + ||b||) on a seeded probe
+        (||J^T|| from below by ||J^T s|| for a random sign vector), refine_T = eta > tau (SEM_REFINE_ETA, default
+        1e-13), refine_eta_T = eta; a non-finite eta raises.  Returns eta."""
+        self._require_T()
+        if self._apply_T is None:
+            raise RuntimeError("set_operator(..., apply_lines_T=...) first")
+        if tau is None:
+            tau = float(os.environ.get("SEM_REFINE_ETA", "1e-13"))
+        amax = self._amax if self._amax is not None else (lambda t: float(t.abs().max()))
+        g = torch.Generator(device=self.device).manual_seed(seed)
+        b = torch.rand((self.NX, self.m), dtype=torch.float64, device=self.device, generator=g) * 2 - 1
+        sgn = torch.sign(torch.rand((self.NX, self.m), dtype=torch.float64, device=self.device, generator=g) - 0.5)
+        self.refine_T = False
+        nJ = amax(self._apply_T(sgn))
+        x = self._solve_lines_T(b)
+        eta = amax(b - self._apply_T(x)) / (nJ * amax(x) + amax(b))
+        if not math.isfinite(eta):
+            raise RuntimeError(f"velocity factor: non-finite backward error of the transposed solve on the probe ({eta})")
+        self.refine_eta_T = eta
+        self.refine_T = eta > tau
+        return eta
+
+    def capture_T(self):
+        """Capture the transposed solve in a hipGraph of its own, with its own input and output buffers (capture's
+        twin; solve_T / solve1_T replay it).  Forward and transposed solves of one solver share the nested solve's
+        work arrays: they are stream-ordered, not concurrent.  Returns False (the solve stays eager) off the GPU or
+        when the device libraries refuse the capture."""
+        self._require_T()
+        if self.device.type != "cuda":
+            return False
+        self._bin_T = torch.zeros((self.NX, self.m), dtype=torch.float64, device=self.device)
+        cur = torch.cuda.current_stream(self.device)
+        s = torch.cuda.Stream(self.device)
+        s.wait_stream(cur)
+        try:
+            with torch.cuda.stream(s):
+                self._solve_lines_T(self._bin_T)      # builds the tables and warms up outside the capture
+            cur.wait_stream(s)
+            g = torch.cuda.CUDAGraph()
+            with no_gc(), torch.cuda.graph(g):
+                self._xout_T = self._solve_lines_T(self._bin_T)
+            self._graph_T = g
+            return True
+        except RuntimeError:
+            torch.cuda.synchronize(self.device)
+            self._graph_T = None
+            return False
+
+    def solve1_T(self, b):
+        """x = A^-T b for a one-component operator (transpose=True); b is a length-N vector in the x-major numbering."""
+        self._require_T()
+        if self.ncomp != 1:
+            raise ValueError("solve1_T needs ncomp=1")
+        NX, NY = self.NX, self.NY
+        if self._graph_T is not None:
+            self._bin_T.copy_(b.reshape(NX, NY))
+            self._graph_T.replay()
+            return self._xout_T.reshape(-1).clone()
+        return self._solve_lines_T(b.reshape(NX, NY).clone()).reshape(-1)
+
     def capture(self):
         """Capture the solve (about 3 (N_ex+1) + 10 launches) in a hipGraph: a Schur-complement
         matvec then costs the kernels, not the Python and launch overhead of that many small ops.
@@ -1247,11 +1587,23 @@ class VelocityJacobianSolver:
         return self._solve_lines(b.reshape(NX, NY).clone()).reshape(-1)
 
     def solve_T(self, bu, bv):
-        """J^T x = b is not available from the line condensation: there is no transposed condensation (the nested
-        interior solves and the interface sweep would both have to run transposed).  The nested-dissection factor
-        has it (NestedDissectionSolver.solve_T)."""
-        raise NotImplementedError("the line-condensation velocity solve has no transposed solve: no transposed "
-                                  "condensation; factor with NestedDissectionSolver for solve_T")
+        """(J^-T [bu; bv]) split as (xu, xv), for a solver built with transpose=True (the transposed condensation:
+        the nested interior solves and the interface sweep both run transposed, _solve_lines_once_T); otherwise
+        NotImplementedError."""
+        self._require_T()
+        if self.ncomp != 2:
+            raise ValueError("solve_T needs ncomp=2; use solve1_T")
+        NX, NY = self.NX, self.NY
+        if self._graph_T is not None:
+            b3 = self._bin_T.view(NX, 2, NY)
+            b3[:, 0, :] = bu.reshape(NX, NY)
+            b3[:, 1, :] = bv.reshape(NX, NY)
+            self._graph_T.replay()
+            out = self._xout_T.view(NX, 2, NY)
+            return out[:, 0, :].reshape(-1).clone(), out[:, 1, :].reshape(-1).clone()
+        B = torch.stack((bu.reshape(NX, NY), bv.reshape(NX, NY)), dim=1).reshape(NX, self.m)
+        out = self._solve_lines_T(B).view(NX, 2, NY)
+        return out[:, 0, :].reshape(-1), out[:, 1, :].reshape(-1)
 
     def solve(self, bu, bv):
         """(J^-1 [bu; bv]) split as (xu, xv); bu, bv are length-N vectors in the x-major numbering."""
