@@ -286,8 +286,20 @@ int sem_basis_update(const double* V, int64_t ldv, int k, int64_t n, const doubl
  * condensation over node lines (see sem_amd/csrc/ns_velocity.hip for the layout): dense
  * interior blocks A_II per element column, dense interface-line blocks D, and the diagonal
  * line-to-line couplings aIB, aBI, E, F.  Rows in the Dirichlet set (dir_mask, or dir_sides when
- * dir_mask is NULL) are identity rows.  Whole-mesh handles only.  Sizes (doubles) from
- * sem_velocity_block_sizes: sizes[0..5] = A_II, D, aIB, aBI, E, F. */
+ * dir_mask is NULL) are identity rows: 1 on the diagonal, 0 in every other piece.  D, E, F, aIB and aBI
+ * are written in full by every call (D, A_II and the condensed pieces are zeroed first); a NULL cu or cv
+ * is a field of ones, a NULL j** a field of zeros.
+ * Strip handles (ex_begin > 0 or ex_end < nex; since ABI 7): the pieces cover the strip's own element
+ * columns [ex_begin, ex_end) and lines; every operand field and dir_mask holds the strip's n_local nodes
+ * (dir_mask indexed from the strip's first line), col_begin / col_end stay global element columns inside
+ * the strip.  The x sums run over the strip's own columns, so the rows of both interface lines of the
+ * strip are partial rows -- the D blocks of a shared line of two neighbouring strips sum to the whole
+ * mesh's block -- and the pointwise terms (juu, juv, jvu, jvv) and the Dirichlet identity diagonal of the
+ * strip's right interface line are left to the strip on its right, which owns that line (ex_end < nex;
+ * the rule of sem_ns_apply): there a Dirichlet row is all zero in this strip's pieces.
+ * Sizes (doubles) from sem_velocity_block_sizes: sizes[0..5] = A_II, D, aIB, aBI, E, F, for the handle's
+ * ne = ex_end - ex_begin columns: ne nI^2, (ne + 1) m^2, ne (P-1) 2 m, ne 2 (P-1) m, ne m, ne m with
+ * m = ncomp N_y and nI = (P-1) m. */
 typedef struct sem_velocity_desc {
   double c_mass, c_stiff, c_gradx, c_grady;
   const double* cu;   /* nullable = ones */
