@@ -19,7 +19,7 @@ ARCH = os.environ.get("SEM_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["sem_ops.hip", "apply_tp.hip", "apply_band.hip", "apply_transpose.hip", "gll_tables.cpp", "krylov_sweeps.hip", "ns_velocity.hip", "ns_apply.hip", "ns_apply_transpose.hip", "block_gemv.hip", "ns_condense.hip",
            "ns_condense_transpose.hip", "dense_inverse.hip", "front_solve.hip", "front_transpose.hip"]
-HEADERS = ["sem_internal.h", "gll_consts.h", "apply_common.h", "apply_select.h", "hip_util.h", "cond_common.h", os.path.join("..", "..", "include", "sem_ops.h")]
+HEADERS = ["sem_internal.h", "gll_consts.h", "apply_common.h", "apply_select.h", "band_tile_map.h", "hip_util.h", "cond_common.h", os.path.join("..", "..", "include", "sem_ops.h")]
 
 
 def _hipcc():

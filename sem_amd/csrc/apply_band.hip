@@ -36,6 +36,7 @@
 
 #include "apply_common.h"
 #include "apply_select.h"
+#include "band_tile_map.h"
 
 namespace sem {
 
@@ -330,6 +331,7 @@ struct BandArgs {
   int mchunk;             // apply_march: element positions marched by one workgroup
   int pos0, pos1;         // element-position range of the launch (struct-argument kernel only; the
                           // preloaded-argument kernel always covers [0, ncols + 1))
+  unsigned ty_mul, ty_packed;  // reciprocal of tiles_y and tiles_y | shift of the tile map (band_tile_map.h)
   // FULL kernels only
   const double* ea;
   const double* eb;
@@ -445,11 +447,12 @@ __device__ const GllWTab<P> kGllW = GllWTab<P>::make();
 // Kernel body.  The fields the prologue needs before its first global load (x, cu, cv pointers and
 // the tile-mapping integers) arrive as separate values: from the struct (apply_band) or as leading
 // scalar kernel arguments that the command processor preloads into SGPRs (apply_band_kp, KP =
-// true), so the first staging load does not wait for a kernarg memory fetch.
+// true), so the first staging load does not wait for a kernarg memory fetch.  ptymul, ptypacked: the tile map's
+// reciprocal of tiles_y and tiles_y | shift (band_tile_map.h); ney, which no staging load needs, comes from the struct.
 template <int P, int TXE, int TYE, int NS, bool FULL, int CM, bool GRAD, bool KP>
 __device__ __forceinline__ void band_body(const double* __restrict__ px, const double* __restrict__ pcu,
                                           const double* __restrict__ pcv, int pNY, int plb0, int pex_begin,
-                                          int pex_end, int pney, int pnblk, int ptiles_y, int pnbytes,
+                                          int pex_end, int ptymul, int pnblk, int ptypacked, int pnbytes,
                                           const BandArgs& a) {
   using C = BCfg<P, TXE, TYE, NS>;
   using PL = EPlan<P, NS>;
@@ -467,13 +470,14 @@ __device__ __forceinline__ void band_body(const double* __restrict__ px, const d
   __shared__ double ws[n];
 
   // XCD-aware remap: blocks b and b+8 share an XCD, so each XCD gets a contiguous run of tiles (y fastest) and
-  // neighbouring tiles share their halo lines through that XCD's L2.
-  const int nb = pnblk, bid = blockIdx.x, tyn = ptiles_y;
-  const int xcd = bid & 7, rk = bid >> 3, q8 = nb >> 3, rem = nb & 7;
-  const int L = (xcd < rem ? xcd * (q8 + 1) : rem * (q8 + 1) + (xcd - rem) * q8) + rk;
-  const int tx = L / tyn, ty = L - tx * tyn;
+  // neighbouring tiles share their halo lines through that XCD's L2.  L / tiles_y is a multiply-high by the
+  // launcher's reciprocal (band_tile_map.h): a runtime division here was ~25 dependent instructions in front of
+  // every workgroup's first load.
+  const BandTile tile = band_tile_map(blockIdx.x, static_cast<unsigned>(pnblk), static_cast<unsigned>(ptymul),
+                                      static_cast<unsigned>(ptypacked));
+  const int tx = tile.tx, ty = tile.ty;
 
-  const int lb0 = plb0, NY = pNY;
+  const int lb0 = plb0, NY = pNY, pney = a.ney;
   // element positions [m0, m1) x [n0, n1); position ex_end (ney) is the ghost holding the closing line (column).
   // KP kernels cover every position; the struct kernel may be restricted to [pos0, pos1) (the multi-GPU overlap
   // applies the interface positions first, then the interior)
@@ -557,6 +561,10 @@ __device__ __forceinline__ void band_body(const double* __restrict__ px, const d
     BPIN(a.cpol);
     BPIN(a.lb1);
     BPIN(a.nex);
+    BPIN(a.ney);
+    // not read here, but fetched by the same s_load as ney, nex and NXg: left dead, its SGPR was reused for a tile-map
+    // temporary, and that write had to wait for the whole kernarg fetch -- in front of the first staging load
+    BPIN(a.tiles_y);
   }
   if constexpr (FULL) {  // both kernels: the epilogue-only fields of the optional terms
     BPIN(a.cE);
@@ -564,6 +572,30 @@ __device__ __forceinline__ void band_body(const double* __restrict__ px, const d
     BPIN(a.has_e1);
     BPIN(a.has_e2);
     BPIN(a.mask);
+  }
+  // ---- the epilogue's tile-uniform decisions, made here in the shadow of the staging loads (behind barrier 2 they
+  // were ~50 scalar instructions on every tile's way to its stores) and carried across the role paths as one SGPR:
+  //   bit 0  special: the tile can hold a Dirichlet row, an extra / accumulate term or a strip-ownership rule
+  //   bit 1  lean:    an ordinary tile of a form without mass term whose given terms need no select (GRAD: cu and
+  //                   cv both given) -- z = xk + yk (+ u xg + v yg) and nothing else.  The Laplacian-only form takes
+  //                   it on MALL-resident meshes only (cache policy 3): at 1024^2 its lean branch measured 2 % slower
+  //                   than the general one (profiles/band_lean/variants.txt), like the smaller LDS footprint above
+  //   bit 2  the y stores are system-scope (cache policy 3)
+  int epi;
+  {
+    bool special = FULL;
+    if (a.dir_mode != SEM_DIR_NONE) {
+      const int gxl = gx0 + rows_ok - 1, gyl = gy0 + cols_ok - 1;
+      const unsigned sd = a.sides;
+      special = special || ((sd & SEM_SIDE_W) && gx0 == 0) || ((sd & SEM_SIDE_E) && gxl >= a.NXg - 1) ||
+                ((sd & SEM_SIDE_S) && gy0 == 0) || ((sd & SEM_SIDE_N) && gyl >= NY - 1);
+    }
+    // fM == 0.0 on its bits (+-0: every bit below the sign clear), so the test stays on the scalar unit
+    const bool no_mass = (static_cast<unsigned long long>(__double_as_longlong(a.fM)) << 1) == 0;
+    const bool cp3 = (a.cpol & 255) == 3;
+    const bool lean = !special && no_mass && (GRAD ? has_u && has_v : cp3);
+    epi = __builtin_amdgcn_readfirstlane((special ? 1 : 0) | (lean ? 2 : 0) | (cp3 ? 4 : 0));
+    asm volatile("" : "+s"(epi));  // formed here, not sunk to its uses
   }
 
   // ---- LDS: staged window, weights
@@ -677,18 +709,13 @@ __device__ __forceinline__ void band_body(const double* __restrict__ px, const d
   __syncthreads();
 
   // ---- epilogue, every wave: node (r, c) = X + Y rows (+ mass) + the pointwise convection terms; Dirichlet rows, the extra /
-  // accumulate terms and the strip-ownership rules only in a tile that can hold one (tile-uniform test)
-  const int NXg = a.NXg;
-  bool special = FULL;
-  if (a.dir_mode != SEM_DIR_NONE) {
-    const int gxl = gx0 + rows_ok - 1, gyl = gy0 + cols_ok - 1;
-    const unsigned sd = a.sides;
-    special = special || ((sd & SEM_SIDE_W) && gx0 == 0) || ((sd & SEM_SIDE_E) && gxl >= NXg - 1) ||
-              ((sd & SEM_SIDE_S) && gy0 == 0) || ((sd & SEM_SIDE_N) && gyl >= NY - 1);
-  }
+  // accumulate terms and the strip-ownership rules only in a tile that can hold one.  The tile-uniform decisions
+  // come from epi (formed before barrier 1): behind this barrier an ordinary tile of the hot form runs the LDS
+  // reads, z = xk + yk, the two fma with u, v and the stores, and nothing else.
+  const bool special = (epi & 1) != 0, lean = (epi & 2) != 0;
   // the LDS reads of all NE nodes are issued before the first use, so a thread pays one LDS round trip (two in a
   // special tile) instead of two per node; the per-node arithmetic below keeps its order
-  double rxk[C::NE], ryk[C::NE], rxg[C::NE], ryg[C::NE], rxv[C::NE] = {};
+  double rxk[C::NE], ryk[C::NE], rxg[C::NE], ryg[C::NE];
 #pragma unroll
   for (int e = 0; e < C::NE; ++e) {
     const int q = tid + e * C::THREADS;
@@ -699,41 +726,56 @@ __device__ __forceinline__ void band_body(const double* __restrict__ px, const d
     rxg[e] = GRAD ? XG[o] : 0.0;
     ryg[e] = GRAD ? YG[o] : 0.0;
   }
-  if (special) {
+  double zz[C::NE];
+  if (lean) {
+#pragma unroll
+    for (int e = 0; e < C::NE; ++e) {
+      double z = rxk[e] + ryk[e];
+      if constexpr (GRAD) {
+        z = fma(pu[e], rxg[e], z);
+        z = fma(pv[e], ryg[e], z);
+      }
+      zz[e] = z;
+    }
+  } else {
+    double rxv[C::NE] = {};
+    if (special) {
+#pragma unroll
+      for (int e = 0; e < C::NE; ++e) {
+        const int q = tid + e * C::THREADS;
+        const int r = q / LW, c = q - r * LW;
+        rxv[e] = Ts[(P + r) * PT + P + c];
+      }
+    }
 #pragma unroll
     for (int e = 0; e < C::NE; ++e) {
       const int q = tid + e * C::THREADS;
       const int r = q / LW, c = q - r * LW;
-      rxv[e] = Ts[(P + r) * PT + P + c];
+      double z = rxk[e] + ryk[e];
+      if (a.fM != 0.0) {   // the mass term (not on the CD / NS hot paths: a uniform branch, its weights from LDS)
+        const int i = r % P, me = m0 + r / P, j = c % P, ne = n0 + c / P;
+        const double mx = i != 0 ? ws[i] : (me - 1 >= pex_begin ? wP : 0.0) + (me < pex_end ? w0 : 0.0);
+        const double my = j != 0 ? ws[j] : (ne - 1 >= 0 ? wP : 0.0) + (ne < pney ? w0 : 0.0);
+        z = fma(a.fM * mx * my, Ts[(P + r) * PT + P + c], z);
+      }
+      if constexpr (GRAD) {
+        z = fma(has_u ? pu[e] : 1.0, rxg[e], z);
+        z = fma(has_v ? pv[e] : 1.0, ryg[e], z);
+      }
+      if (special && eoff[e] >= 0) z = finish_node<FULL>(a, NY, pex_end, ops[e], gx0 + r, gy0 + c, rxv[e], z);
+      zz[e] = z;
     }
   }
-  double zz[C::NE];
+  // The stores carry no exec mask: a node that is not the tile's has eoff = -(1 << 26), a byte offset of -(1 << 29)
+  // = 0xE0000000 as the buffer instruction reads it.  ry is a raw resource (stride 0) of num_records = nbytes =
+  // 8 n_local < 2^31 bytes (band_fits), and a raw buffer store whose offset + 8 exceeds num_records is dropped by
+  // the range check -- the same rule that makes the u, v loads at that offset return 0 without touching memory.
+  if ((epi & 4) != 0) {   // system-scope stores (a mesh whose working set stays in the MALL)
 #pragma unroll
-  for (int e = 0; e < C::NE; ++e) {
-    const int q = tid + e * C::THREADS;
-    const int r = q / LW, c = q - r * LW;
-    double z = rxk[e] + ryk[e];
-    if (a.fM != 0.0) {   // the mass term (not on the CD / NS hot paths: a uniform branch, its weights from LDS)
-      const int i = r % P, me = m0 + r / P, j = c % P, ne = n0 + c / P;
-      const double mx = i != 0 ? ws[i] : (me - 1 >= pex_begin ? wP : 0.0) + (me < pex_end ? w0 : 0.0);
-      const double my = j != 0 ? ws[j] : (ne - 1 >= 0 ? wP : 0.0) + (ne < pney ? w0 : 0.0);
-      z = fma(a.fM * mx * my, Ts[(P + r) * PT + P + c], z);
-    }
-    if constexpr (GRAD) {
-      z = fma(has_u ? pu[e] : 1.0, rxg[e], z);
-      z = fma(has_v ? pv[e] : 1.0, ryg[e], z);
-    }
-    if (special && eoff[e] >= 0) z = finish_node<FULL>(a, NY, pex_end, ops[e], gx0 + r, gy0 + c, rxv[e], z);
-    zz[e] = z;
-  }
-  if ((a.cpol & 255) == 3) {   // system-scope stores (a mesh whose working set stays in the MALL)
-#pragma unroll
-    for (int e = 0; e < C::NE; ++e)
-      if (eoff[e] >= 0) bstore_c<17>(ry, eoff[e] * 8, zz[e]);
+    for (int e = 0; e < C::NE; ++e) bstore_c<17>(ry, eoff[e] * 8, zz[e]);
   } else {
 #pragma unroll
-    for (int e = 0; e < C::NE; ++e)
-      if (eoff[e] >= 0) bstore(ry, eoff[e] * 8, zz[e]);
+    for (int e = 0; e < C::NE; ++e) bstore(ry, eoff[e] * 8, zz[e]);
   }
 }
 
@@ -756,7 +798,8 @@ __global__ __launch_bounds__((BCfg<P, TXE, TYE, NS>::THREADS)) void apply_band(c
   BPIN(a.ney);
   BPIN(a.nex);
   BPIN(a.NXg);
-  BPIN(a.tiles_y);
+  BPIN(a.ty_mul);
+  BPIN(a.ty_packed);
   BPIN(a.nbytes);
   BPIN(a.dir_mode);
   if constexpr (kDiag) BPIN(a.diag);
@@ -766,17 +809,18 @@ __global__ __launch_bounds__((BCfg<P, TXE, TYE, NS>::THREADS)) void apply_band(c
   BPIN(a.nblk);
   BPIN(a.cpol);
   band_body<P, TXE, TYE, NS, FULL, CM, GRAD, false>(a.x, (a.flags & 1) ? a.cu : nullptr, (a.flags & 2) ? a.cv : nullptr,
-                                                     a.NY, a.lb0, a.ex_begin, a.ex_end, a.ney, a.nblk, a.tiles_y,
-                                                     a.nbytes, a);
+                                                     a.NY, a.lb0, a.ex_begin, a.ex_end, static_cast<int>(a.ty_mul), a.nblk,
+                                                     static_cast<int>(a.ty_packed), a.nbytes, a);
 }
 
 // Same kernel with the prologue's fields as leading scalar arguments (14 SGPRs, preloaded by the
-// command processor when the code object asks for it: -amdgpu-kernarg-preload-count in build.py).
+// command processor when the code object asks for it: -amdgpu-kernarg-preload-count in build.py).  The two words of
+// the tile map travel as int, like their neighbours.
 template <int P, int TXE, int TYE, int NS, bool FULL, int CM, bool GRAD = true>
 __global__ __launch_bounds__((BCfg<P, TXE, TYE, NS>::THREADS)) void apply_band_kp(
-    const double* px, const double* pcu, const double* pcv, int pNY, int plb0, int pex_begin, int pex_end, int pney,
-    int pnblk, int ptiles_y, int pnbytes, const BandArgs a) {
-  band_body<P, TXE, TYE, NS, FULL, CM, GRAD, true>(px, pcu, pcv, pNY, plb0, pex_begin, pex_end, pney, pnblk, ptiles_y,
+    const double* px, const double* pcu, const double* pcv, int pNY, int plb0, int pex_begin, int pex_end, int ptymul,
+    int pnblk, int ptypacked, int pnbytes, const BandArgs a) {
+  band_body<P, TXE, TYE, NS, FULL, CM, GRAD, true>(px, pcu, pcv, pNY, plb0, pex_begin, pex_end, ptymul, pnblk, ptypacked,
                                                     pnbytes, a);
 }
 
@@ -831,17 +875,23 @@ static int launch_band(const ApplyArgs& g, const sem_handle* h, hipStream_t s) {
   const int tiles_x = (pos1 - pos0 + TXE - 1) / TXE;
   const int tiles_y = (h->ney + 1 + TYE - 1) / TYE;
   const long long nblk = static_cast<long long>(tiles_x) * tiles_y;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return set_error(SEM_EINVAL, "mesh too large for one launch");
+  if (nblk <= 0 || nblk > static_cast<long long>(kBandTileMax) || tiles_y >= (1 << kBandTyBits))
+    return set_error(SEM_EINVAL, "mesh too large for one launch");
   BandArgs b = band_args(g);
   b.pos0 = pos0;
   b.pos1 = pos1;
   b.tiles_y = tiles_y;
+  const BandTileDiv td = band_tile_div(static_cast<uint32_t>(tiles_y));  // exact for every L < nblk (band_tile_map.h)
+  b.ty_mul = td.mul;
+  b.ty_packed = td.packed;
   b.nblk = static_cast<int>(nblk);
   const bool full = g.has_e1 || g.has_e2 || g.cA != 0.0 || g.mask || g.dval;
   const bool grad = g.cX != 0.0 || g.cY != 0.0;
   const dim3 grid(static_cast<unsigned>(nblk)), block(C::THREADS);
   if (tune(SEM_TUNE_BAND_KP) >= 0 && !ranged) {  // -1 (SEM_BAND_KP=0): struct-only arguments (A/B)
-#define SEM_KP_ARGS b.x, b.cu, b.cv, b.NY, b.lb0, b.ex_begin, b.ex_end, b.ney, b.nblk, b.tiles_y, b.nbytes, b
+#define SEM_KP_ARGS                                                                                       \
+  b.x, b.cu, b.cv, b.NY, b.lb0, b.ex_begin, b.ex_end, static_cast<int>(b.ty_mul), b.nblk, static_cast<int>(b.ty_packed), \
+      b.nbytes, b
     if (full && grad)
       hipLaunchKernelGGL((apply_band_kp<P, TXE, TYE, NS, true, CM, true>), grid, block, 0, s, SEM_KP_ARGS);
     else if (full)

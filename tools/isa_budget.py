@@ -15,7 +15,10 @@ even-odd plan's fp64 operation count per wave beside them, so the overhead is ex
   * the LDS wait points of the epilogue: s_waitcnt instructions with an lgkmcnt field that follow at least one LDS read
     since the previous one (a static count over all epilogue paths, the off-path Dirichlet / mass blocks included).
 
-    python tools/isa_budget.py [--order 8] [--cm 0] [--grad 1] [--chain]
+--entry: the instruction index of the first load through the x buffer resource (what a workgroup executes before its
+longest latency starts) and the number of instructions from the last barrier to the last buffer_store.
+
+    python tools/isa_budget.py [--order 8] [--cm 0] [--grad 1] [--chain | --entry]
     python tools/isa_budget.py --source ns_apply.hip --symbol 'ns_apply_band.*Li8E' --chain
     python tools/isa_budget.py --asm FILE ...        # an assembly file made earlier (compile() below)
 """
@@ -177,6 +180,37 @@ def chain_text(name, body):
     return "\n".join(lines)
 
 
+def entry(body):
+    """The two ends of a workgroup's chain that tile-uniform bookkeeping can lengthen: a dict of
+    first_x_load   instruction index of the first buffer_load (the staging loads go through x's buffer resource and
+                   are the kernel's first buffer loads; the weight / coefficient tables before them are global_load)
+    tail           instructions after the last s_barrier up to and including the last buffer_store (labels not
+                   counted): a static count over every epilogue path
+    rcp_before_barrier  v_rcp* instructions in front of the first barrier (a runtime integer division)
+    waits_before_load   s_waitcnt instructions in front of the first buffer load: one belongs to the fallback
+                        prologue of the preloaded arguments; any other puts a kernarg or table fetch in front of
+                        the staging loads."""
+    bars = barriers(body)
+    loads = [i for i, t in enumerate(body) if t.startswith("buffer_load")]
+    stores = [i for i, t in enumerate(body) if t.startswith("buffer_store")]
+    if not loads or not stores:
+        raise ValueError("the kernel has no buffer load or no buffer store")
+    tail = sum(1 for t in body[bars[-1] + 1:stores[-1] + 1] if not t.endswith(":"))
+    rcp = [(i, t) for i, t in enumerate(body[:bars[0]]) if t.startswith("v_rcp")]
+    waits = [(i, t) for i, t in enumerate(body[:loads[0]]) if t.startswith("s_waitcnt")]
+    return {"first_x_load": loads[0], "tail": tail, "rcp_before_barrier": rcp, "waits_before_load": waits,
+            "barriers": bars}
+
+
+def entry_text(name, body):
+    e = entry(body)
+    return "\n".join([f"kernel {name}", f"  instructions {len(body)}, s_barrier at {e['barriers']}",
+                      f"  first load through the x buffer resource: instruction {e['first_x_load']}",
+                      f"  instructions from the last barrier to the last buffer_store: {e['tail']}",
+                      f"  v_rcp in front of the first barrier: {len(e['rcp_before_barrier'])}",
+                      f"  s_waitcnt in front of the first buffer load: {[i for i, _ in e['waits_before_load']]}"])
+
+
 def resources(remarks_text, symbol):
     """{kernel symbol: {field: int}} from the compiler's kernel-resource-usage remarks, kernels matching `symbol`."""
     rx, out, cur = re.compile(symbol), {}, None
@@ -233,6 +267,7 @@ def main():
     ap.add_argument("--grad", type=int, default=1)
     ap.add_argument("--full", type=int, default=0)
     ap.add_argument("--chain", action="store_true")
+    ap.add_argument("--entry", action="store_true", help="first staging load and the tail behind the last barrier")
     ap.add_argument("--resources", action="store_true", help="registers, LDS, occupancy of the band kernel per order")
     ap.add_argument("--remarks", default="", help="with --resources: a remarks file made earlier")
     a = ap.parse_args()
@@ -250,6 +285,9 @@ def main():
     name, body = kernel_body(lines, symbol)
     if a.chain:
         print(chain_text(name, body))
+        return 0
+    if a.entry:
+        print(entry_text(name, body))
         return 0
     print(f"kernel {name}")
     total = collections.Counter()
