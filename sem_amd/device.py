@@ -348,3 +348,24 @@ def no_gc():
     finally:
         if enabled:
             gc.enable()
+
+
+def capture_graph(device, fn):
+    """Capture fn() in a hipGraph: one call of fn on a side stream first (the warm-up outside the capture: library
+    workspaces, lazily built tables), then the capture on the current stream under no_gc().  Returns (graph, fn's
+    output inside the capture); (None, None) after a synchronise when the device libraries refuse, and the
+    caller stays eager.  fn must read its input from a buffer that lives as long as the graph."""
+    cur = torch.cuda.current_stream(device)
+    s = torch.cuda.Stream(device)
+    s.wait_stream(cur)
+    try:
+        with torch.cuda.stream(s):
+            fn()
+        cur.wait_stream(s)
+        g = torch.cuda.CUDAGraph()
+        with no_gc(), torch.cuda.graph(g):
+            out = fn()
+        return g, out
+    except RuntimeError:
+        torch.cuda.synchronize(device)
+        return None, None

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from .. import SEM, _lib
-from ..device import get_mesh, no_gc
+from ..device import capture_graph, get_mesh, no_gc
 from ..krylov import Recycle, gcro, gmres
 from ..operators import ConvectionTensor, SEMOperator
 from ..tracing import phase
@@ -822,21 +822,7 @@ class _SchurComplement:
         return rc
 
     def _capture(self):
-        dev = self.ns._mesh.device
-        cur = torch.cuda.current_stream(dev)
-        s = torch.cuda.Stream(dev)
-        s.wait_stream(cur)
-        try:
-            with torch.cuda.stream(s):
-                self._body(self._x)   # warm-up outside the capture (library workspaces)
-            cur.wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with no_gc(), torch.cuda.graph(g):
-                self._out = self._body(self._x)
-            self._graph = g
-        except RuntimeError:
-            torch.cuda.synchronize(dev)
-            self._graph = None
+        self._graph, self._out = capture_graph(self.ns._mesh.device, lambda: self._body(self._x))
 
     def __call__(self, dp):
         if self._graph is None:

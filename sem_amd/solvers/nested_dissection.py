@@ -38,10 +38,10 @@ Bytes per solve (cfg5: 128^2 elements, P = 12): the split leaves' blobs and V_e,
 (StripNDSolver).  The algebra runs on any torch device: the CPU path (a per-front loop over the same tables) is
 what the CPU tests check against SciPy's sparse solve.
 
-The same factor solves J^T x = b (solve_T, solve1_T, capture_T, check_refinement_T): the transposed factors applied
-in the reverse order over the stored operators (_build_steps_T; HIP steps in csrc/front_transpose.hip), no operator
-stored twice, the plan built on the first transposed solve.  Whole mesh only: StripNDSolver refuses (no transposed
-reduced system), as does the line condensation (no transposed condensation).
+The same factor solves J^T x = b (_solve_lines_once_T under the inherited solve_T, solve1_T, capture_T,
+check_refinement_T): the transposed factors applied in the reverse order over the stored operators (_build_steps_T;
+HIP steps in csrc/front_transpose.hip), no operator stored twice, the plan built on the first transposed solve.
+Whole mesh only: StripNDSolver refuses (no transposed reduced system).
 """
 import functools
 import math
@@ -278,10 +278,12 @@ def _gll_tables(P):
 
 
 class NestedDissectionSolver(VelocityJacobianSolver):
-    """x = J^-1 b for the velocity Jacobian J of one linearisation by nested dissection (module docstring).  Same
-    interface as VelocityJacobianSolver (solve, solve1, _solve_lines, set_operator, check_refinement, capture), plus
-    the transposed solve J^-T b from the same factor (solve_T, solve1_T, _solve_lines_T, check_refinement_T, capture_T);
-    factor with factor_mesh(mesh, **kw) (the device mesh) or factor_coeffs(dx, dy, **kw) (any torch device)."""
+    """x = J^-1 b for the velocity Jacobian J of one linearisation by nested dissection (module docstring).  The
+    interface is VelocityJacobianSolver's, inherited with its solve driver (solve, solve1, _solve_lines,
+    set_operator, check_refinement, capture and their _T twins for J^-T b from the same factor); what is this
+    class's own are the line solves _solve_lines_once and _solve_lines_once_T over its plans and _require_T (every
+    factor serves the transposed solve).  Factor with factor_mesh(mesh, **kw) (the device mesh) or
+    factor_coeffs(dx, dy, **kw) (any torch device)."""
 
     def __init__(self, P, nex, ney, device, ncomp=2, cols=None):
         """cols = (xa, xb): the element columns of a strip of the nex x ney mesh (StripNDSolver); the solver's
@@ -291,11 +293,8 @@ class NestedDissectionSolver(VelocityJacobianSolver):
         self.interior = "nd"
         self.tree = nd_tree(P, nex, ney, ncomp, xa, xb)
         self.chunk_elems = int(os.environ.get("SEM_ND_CHUNK", "2048"))
-        # transposed solve (solve_T): its plan is built on first use; refine_T is check_refinement_T's gate
-        self._steps_T = self._hip_T = self._stage_T = self._graph_T = None
-        self._apply_T = None
-        self.refine_T = False
-        self.refine_eta_T = None
+        # transposed solve (solve_T): its plan is built on first use
+        self._steps_T = self._hip_T = self._stage_T = None
 
     # ------------------------------------------------------------------ factorisation
     def factor_mesh(self, mesh, budget_bytes=24 << 30, **kw):
@@ -721,6 +720,19 @@ class NestedDissectionSolver(VelocityJacobianSolver):
         return dict(copy_tgt=copy_tgt.astype(np.int64), copy_src=copy_src.astype(np.int64), acc_tgt=uniq,
                     acc_src=src4)
 
+    @staticmethod
+    def _scatter(Wz, stage, sc):
+        """The torch form of sem_front_scatter on a _scatter_plan: the copies from the stage, then every accumulation
+        target minus its up to four stage entries, in their fixed order."""
+        ct, cs, at, a4 = (torch.as_tensor(sc[k], device=Wz.device) for k in ("copy_tgt", "copy_src", "acc_tgt",
+                                                                             "acc_src"))
+        Wz[ct] = stage[cs]
+        v = Wz[at]
+        for k in range(4):
+            s = a4[:, k]
+            v = v - torch.where(s >= 0, stage[s.clamp(min=0)], torch.zeros_like(v))
+        Wz[at] = v
+
     # ------------------------------------------------------------------ solve
     def _solve_lines_once(self, B):
         """Forward steps, the strip hook (the reduced system over the strip-boundary lines; nothing on a whole mesh),
@@ -763,15 +775,7 @@ class NestedDissectionSolver(VelocityJacobianSolver):
                     y = stage[:sp["nitems"] * sp["stride"]].view(sp["nitems"], sp["stride"])
                     yi = y[:, torch.as_tensor(sp["pat"], device=dev)]                 # (items, nrows, nnz)
                     y[:, sp["out_off"]:sp["out_off"] + sp["pat"].shape[0]] = (sp["coef"] * yi).sum(-1)
-                sc = st[2]
-                ct, cs, at, a4 = (torch.as_tensor(sc[k], device=dev) for k in ("copy_tgt", "copy_src", "acc_tgt",
-                                                                                "acc_src"))
-                Wz[ct] = stage[cs]
-                v = Wz[at]
-                for k in range(4):
-                    s = a4[:, k]
-                    v = v - torch.where(s >= 0, stage[s.clamp(min=0)], torch.zeros_like(v))
-                Wz[at] = v
+                self._scatter(Wz, stage, st[2])
             else:
                 for T, q, xidx, yidx in st[1]:
                     x = Wz[torch.as_tensor(xidx, device=dev)]
@@ -832,111 +836,12 @@ class NestedDissectionSolver(VelocityJacobianSolver):
                 for T, q, r0, r1, xidx, off in st[1]:
                     x = Wz[torch.as_tensor(xidx, device=dev)]
                     stage[off:off + T.shape[2]] = T[q, r0:r1].t() @ x
-                sc = st[2]
-                ct, cs, at, a4 = (torch.as_tensor(sc[k], device=dev) for k in ("copy_tgt", "copy_src", "acc_tgt",
-                                                                                "acc_src"))
-                Wz[ct] = stage[cs]
-                v = Wz[at]
-                for k in range(4):
-                    s = a4[:, k]
-                    v = v - torch.where(s >= 0, stage[s.clamp(min=0)], torch.zeros_like(v))
-                Wz[at] = v
+                self._scatter(Wz, stage, st[2])
 
-    def _solve_lines_T(self, B):
-        """x = J^-T b with b, x as (NX, ncomp NY) line arrays; with `refine_T` set, one step of iterative refinement
-        on the transposed matrix-free apply (set_operator's apply_lines_T)."""
-        X = self._solve_lines_once_T(B)
-        if self.refine_T:
-            if self._apply_T is None:
-                raise RuntimeError("refine_T is set but no transposed operator: set_operator(..., apply_lines_T=...)")
-            X = X + self._solve_lines_once_T(B - self._apply_T(X))
-        return X
-
-    def set_operator(self, apply_lines, amax=None, apply_lines_T=None):
-        """As VelocityJacobianSolver.set_operator; apply_lines_T(X) -> J^T X on (NX, m) line arrays is the operator of
-        check_refinement_T and of the transposed solve's refinement step."""
-        super().set_operator(apply_lines, amax)
-        self._apply_T = apply_lines_T
-
-    def check_refinement_T(self, tau=None, seed=17):
-        """check_refinement's twin for J^T x = b: the transposed solve's normwise backward error on a seeded probe
-        (||J^T|| from below by ||J^T s|| for a random sign vector), refine_T = eta > tau (SEM_REFINE_ETA, default
-        1e-13), refine_eta_T = eta; a non-finite eta raises.  Returns eta."""
-        if self._apply_T is None:
-            raise RuntimeError("set_operator(..., apply_lines_T=...) first")
-        if self._amax is None:
-            self._amax = lambda t: float(t.abs().max())
-        if tau is None:
-            tau = float(os.environ.get("SEM_REFINE_ETA", "1e-13"))
-        g = torch.Generator(device=self.device).manual_seed(seed)
-        b = torch.rand((self.NX, self.m), dtype=torch.float64, device=self.device, generator=g) * 2 - 1
-        sgn = torch.sign(torch.rand((self.NX, self.m), dtype=torch.float64, device=self.device, generator=g) - 0.5)
-        self.refine_T = False
-        nJ = self._amax(self._apply_T(sgn))
-        x = self._solve_lines_T(b)
-        eta = self._amax(b - self._apply_T(x)) / (nJ * self._amax(x) + self._amax(b))
-        if not math.isfinite(eta):
-            raise RuntimeError(f"velocity factor: non-finite backward error on the transposed probe ({eta}): a "
-                               "singular or overflowing pivot block")
-        self.refine_eta_T = eta
-        self.refine_T = eta > tau
-        return eta
-
-    def capture_T(self):
-        """Capture the transposed solve in a second hipGraph with its own input and output buffers (capture()'s
-        twin; solve_T / solve1_T replay it).  Forward and transposed solves of one solver are stream-ordered, not
-        concurrent.  Returns False (the transposed solve stays eager) if the capture is refused."""
-        if self.device.type != "cuda" or not self.factored:
-            return False
-        from .velocity_solve import no_gc
-        self._bin_T = torch.zeros((self.NX, self.m), dtype=torch.float64, device=self.device)
-        cur = torch.cuda.current_stream(self.device)
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(cur)
-        try:
-            with torch.cuda.stream(s):
-                self._solve_lines_T(self._bin_T)      # builds the plan and warms up outside the capture
-            cur.wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with no_gc(), torch.cuda.graph(g):
-                self._xout_T = self._solve_lines_T(self._bin_T)
-            self._graph_T = g
-            return True
-        except RuntimeError:
-            torch.cuda.synchronize(self.device)
-            self._graph_T = None
-            return False
-
-    def solve1_T(self, b):
-        """x = A^-T b for a one-component operator; b is a length-N vector in the x-major numbering."""
+    def _require_T(self):
+        """Every factor serves the transposed solve (its plan is built on the first one)."""
         if not self.factored:
             raise RuntimeError("factor() first")
-        if self.ncomp != 1:
-            raise ValueError("solve1_T needs ncomp=1")
-        NX, NY = self.NX, self.NY
-        if self._graph_T is not None:
-            self._bin_T.copy_(b.reshape(NX, NY))
-            self._graph_T.replay()
-            return self._xout_T.reshape(-1).clone()
-        return self._solve_lines_T(b.reshape(NX, NY).clone()).reshape(-1)
-
-    def solve_T(self, bu, bv):
-        """(J^-T [bu; bv]) split as (xu, xv), from the same factor as solve (no second copy of the operators)."""
-        if not self.factored:
-            raise RuntimeError("factor() first")
-        if self.ncomp != 2:
-            raise ValueError("solve_T needs ncomp=2; use solve1_T")
-        NX, NY = self.NX, self.NY
-        if self._graph_T is not None:
-            b3 = self._bin_T.view(NX, 2, NY)
-            b3[:, 0, :] = bu.reshape(NX, NY)
-            b3[:, 1, :] = bv.reshape(NX, NY)
-            self._graph_T.replay()
-            out = self._xout_T.view(NX, 2, NY)
-            return out[:, 0, :].reshape(-1).clone(), out[:, 1, :].reshape(-1).clone()
-        B = torch.stack((bu.reshape(NX, NY), bv.reshape(NX, NY)), dim=1).reshape(NX, self.m)
-        out = self._solve_lines_T(B).view(NX, 2, NY)
-        return out[:, 0, :].reshape(-1), out[:, 1, :].reshape(-1)
 
     # sem_front_gemv_t from this median operand-row count on (_launch_form_T)
     T_MIN_ROWS = 48
@@ -989,12 +894,7 @@ class NestedDissectionSolver(VelocityJacobianSolver):
         nW = self.NX * self.m
         self._stage_T = torch.zeros(self._stage_len_T, dtype=torch.float64, device=dev)
         P, nb = self.P, self.tree.nb
-
-        def i32(a):
-            a = np.ascontiguousarray(a, dtype=np.int64)
-            if a.size and (a.min() < -1 or a.max() >= 2 ** 31 - 1):
-                raise AssertionError("nested dissection: index outside int32")
-            return torch.as_tensor(a.astype(np.int32), device=dev)
+        i32 = self._i32
 
         def leaf_tables(L, ncoef, nint):
             iidx, bidx, ipat, brow = (np.asarray(L[k]) for k in ("iidx", "bidx", "ipat", "brow"))
@@ -1103,7 +1003,7 @@ class NestedDissectionSolver(VelocityJacobianSolver):
                                          keep["dims"].data_ptr(), keep["xoff"].data_ptr(), keep["yoff"].data_ptr(),
                                          keep["poff"].data_ptr(), keep["tiles"].data_ptr(), keep["xidx"].data_ptr(),
                                          yptr, None, sptr, None)
-            sc = None if back else self._scatter_tables(st[2], nW, i32, self._stage_len_T)
+            sc = None if back else self._scatter_tables(st[2], nW, self._stage_len_T)
             plan.append(("gemvT", d, keep, sc))
         self._partials_T = torch.zeros(max(npart, 1), dtype=torch.float64, device=dev)
         for kind, d, _, _ in plan:
@@ -1135,9 +1035,20 @@ class NestedDissectionSolver(VelocityJacobianSolver):
                 else:
                     _lib.check(lib.sem_front_gemv(C.byref(d), st))
                 if sc is not None:
-                    _lib.check(lib.sem_front_scatter(sc["n_copy"], sc["ct"].data_ptr(), sc["cs"].data_ptr(),
-                                                     sc["n_acc"], sc["at"].data_ptr(), sc["a4"].data_ptr(),
-                                                     self._stage_T.data_ptr(), Wz.data_ptr(), st))
+                    _lib.check(self._launch_scatter(lib, sc, self._stage_T, Wz, st))
+
+    def _i32(self, a):
+        """Index table a (-1: absent) as an int32 device tensor, checked to fit."""
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        if a.size and (a.min() < -1 or a.max() >= 2 ** 31 - 1):
+            raise AssertionError("nested dissection: index outside int32")
+        return torch.as_tensor(a.astype(np.int32), device=self.device)
+
+    @staticmethod
+    def _launch_scatter(lib, sc, stage, Wz, st):
+        """One sem_front_scatter launch on stream st over the tables sc (_scatter_tables); returns its status."""
+        return lib.sem_front_scatter(sc["n_copy"], sc["ct"].data_ptr(), sc["cs"].data_ptr(), sc["n_acc"],
+                                     sc["at"].data_ptr(), sc["a4"].data_ptr(), stage.data_ptr(), Wz.data_ptr(), st)
 
     def _hip_plan(self):
         """Device tables of every step (sem_front_gemv descriptors, sem_front_scatter index arrays), checked on the
@@ -1147,17 +1058,11 @@ class NestedDissectionSolver(VelocityJacobianSolver):
         nW = self.NX * self.m
         self._stage = torch.zeros(self._stage_len, dtype=torch.float64, device=dev)
         plan = []
-
-        def i32(a):
-            a = np.ascontiguousarray(a, dtype=np.int64)
-            if a.size and (a.min() < -1 or a.max() >= 2 ** 31 - 1):
-                raise AssertionError("nested dissection: index outside int32")
-            return torch.as_tensor(a.astype(np.int32), device=dev)
-
+        i32 = self._i32
         transposed = {}     # id(group tensor) -> its operators transposed (form 1)
         for st in self._steps:
             if st[0] == "leaf":
-                plan.append(self._leaf_plan(st, nW, i32))
+                plan.append(self._leaf_plan(st, nW))
                 continue
             items, back = st[1], st[0] == "back"
             nf = len(items)
@@ -1230,7 +1135,7 @@ class NestedDissectionSolver(VelocityJacobianSolver):
                                     keep["tiles"].data_ptr(), keep["xidx"].data_ptr(),
                                     keep["yidx"].data_ptr() if back else None, None,
                                     None if back else self._stage.data_ptr())
-            sc = None if back else self._scatter_tables(st[2], nW, i32)
+            sc = None if back else self._scatter_tables(st[2], nW)
             sp = None
             if not back and st[3] is not None:
                 q = st[3]
@@ -1246,7 +1151,8 @@ class NestedDissectionSolver(VelocityJacobianSolver):
             plan.append((d, keep, sc, sp))
         return plan
 
-    def _scatter_tables(self, p, nW, i32, stage_len=None):
+    def _scatter_tables(self, p, nW, stage_len=None):
+        i32 = self._i32
         stage_len = self._stage_len if stage_len is None else stage_len
         for a, hi in ((p["copy_tgt"], nW), (p["acc_tgt"], nW)):
             if a.size and (a.min() < 0 or a.max() >= hi):
@@ -1259,7 +1165,7 @@ class NestedDissectionSolver(VelocityJacobianSolver):
         return dict(n_copy=len(p["copy_tgt"]), ct=i32(p["copy_tgt"]), cs=i32(p["copy_src"]), n_acc=len(p["acc_tgt"]),
                     at=i32(p["acc_tgt"]), a4=i32(p["acc_src"]).contiguous())
 
-    def _leaf_plan(self, st, nW, i32):
+    def _leaf_plan(self, st, nW):
         """The split leaves' sem_leaf_forward descriptor, its tables checked on the host: interior targets distinct
         line entries, boundary patterns inside [y_u; y_v], the boundary rows inside the stage."""
         from .. import _lib
@@ -1273,10 +1179,10 @@ class NestedDissectionSolver(VelocityJacobianSolver):
                 or B.shape != (E, 2 * n * ld + 2 * ld + (self.P - 1) * nb) or not B.is_contiguous()
                 or B.data_ptr() % 16 or B.shape[1] % 2 or B.device != self.device):
             raise AssertionError("nested dissection: bad split-leaf step")
-        keep = dict(iidx=i32(iidx), pat=i32(pat))
+        keep = dict(iidx=self._i32(iidx), pat=self._i32(pat))
         d = _lib.SemLeafLaunch(E, n, ld, nb, self.P - 1, B.shape[1], B.data_ptr(), keep["iidx"].data_ptr(),
                                keep["pat"].data_ptr(), None, self._stage.data_ptr(), L["sstride"], L["soff"])
-        return d, keep, self._scatter_tables(st[2], nW, i32), None
+        return d, keep, self._scatter_tables(st[2], nW), None
 
     def _launch(self, lib, entry, Wz, st):
         """One planned step on stream st: its gemv (or split-leaf) launch, sparse rows, scatter."""
@@ -1293,9 +1199,7 @@ class NestedDissectionSolver(VelocityJacobianSolver):
                                                  sp["pat"].data_ptr(), self._stage.data_ptr(), sp["stride"],
                                                  sp["out_off"], st))
         if sc is not None:
-            _lib.check(lib.sem_front_scatter(sc["n_copy"], sc["ct"].data_ptr(), sc["cs"].data_ptr(), sc["n_acc"],
-                                             sc["at"].data_ptr(), sc["a4"].data_ptr(), self._stage.data_ptr(),
-                                             Wz.data_ptr(), st))
+            _lib.check(self._launch_scatter(lib, sc, self._stage, Wz, st))
 
     def _launch_form(self, back, nf, K, leaves):
         """sem_front_gemv's form for one launch (`forms` = "auto", or "rows" for every launch in form 0): 1 (columns:

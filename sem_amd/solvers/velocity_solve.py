@@ -29,7 +29,7 @@ import time
 
 import torch
 
-from ..device import no_gc
+from ..device import capture_graph
 from ..tracing import phase
 
 GEMV_LDS_DOUBLES = 8192   # sem_block_gemv stages S m operand doubles in LDS (include/sem_ops.h)
@@ -427,10 +427,13 @@ class VelocityJacobianSolver:
     """x = J^-1 b for the velocity Jacobian J of one linearisation, J given by its condensation pieces."""
 
     def __init__(self, P, nex, ney, device, interior="nested", sweep="auto", ncomp=2, transpose=False):
-        """transpose: the factor also serves J^T x = b (solve_T, solve1_T, _solve_lines_T, check_refinement_T,
-        capture_T) from the operators it stores for the forward solve -- the nested interior only; what the
-        transposed solve needs beyond them (two permuted copies of the line couplings, index tables) is built on
-        its first use.  The forward factor and its solves are the same with or without it.
+        """transpose: the factor also serves J^T x = b from the operators it stores for the forward solve -- the
+        nested interior only; what the transposed solve needs beyond them (two permuted copies of the line
+        couplings, index tables) is built on its first use.  The forward factor and its solves are the same with or
+        without it.  The entry points of both directions (solve / solve_T, solve1 / solve1_T, _solve_lines /
+        _solve_lines_T, check_refinement / check_refinement_T, capture / capture_T) are wrappers of one driver
+        ("the solve driver" below), which subclasses inherit: they supply _solve_lines_once, _solve_lines_once_T and
+        _require_T.
         ncomp: unknowns per node -- 2 for the velocity pair [u | v], 1 for a scalar operator
         (the convection-diffusion Jacobian, or the pressure stiffness of the Schur preconditioner).
         interior: elimination of the element-column interiors ("nested" static condensation, or
@@ -452,11 +455,8 @@ class VelocityJacobianSolver:
             raise NotImplementedError("the transposed line condensation needs interior='nested' (the dense column "
                                       "interiors keep A_II^-1 A_IB, not what its transpose needs)")
         self.transpose = bool(transpose)
-        # transposed solve: tables built on its first use (_transpose_tables); refine_T is check_refinement_T's gate
-        self._aIBp = self._aBIp = self._cr_T = self._graph_T = None
-        self._apply_T = None
-        self.refine_T = False
-        self.refine_eta_T = None
+        # transposed solve: tables built on its first use (_require_T, _cr_tables_T)
+        self._aIBp = self._aBIp = self._cr_T = None
         self.sweep, self.ncomp = sweep, ncomp
         self.P, self.nex, self.ney = P, nex, ney
         self.NY, self.NX = ney * P + 1, nex * P + 1
@@ -495,10 +495,13 @@ class VelocityJacobianSolver:
         # conditioned than J (kappa 2.0e6 against kappa(J) = 9.8e3 for the one-component Pe = 1000 operator on
         # 2 x 2 elements, P = 6) the solve's backward error is ~1e-11 where SuperLU's pivoting gives ~4e-17
         # (NavierStokes_Solver.py:184); one refinement step brings it to 3e-17 (tools/backward_error_probe.py)
-        self._apply = None
+        # The driver's state per direction (forward, and _T: transposed): the operator of set_operator, the gate's
+        # decision and its eta, the captured graph of the line solve
+        self._apply = self._apply_T = None
         self._amax = None
-        self.refine = False
-        self.refine_eta = None
+        self.refine = self.refine_T = False
+        self.refine_eta = self.refine_eta_T = None
+        self._graph = self._graph_T = None
 
     @contextlib.contextmanager
     def _phase(self, name):
@@ -1270,9 +1273,33 @@ class VelocityJacobianSolver:
             z[L] -= self.Uh[L] @ z[L + 1]
         return z
 
-    def _solve_lines_hip(self, B):
-        """_solve_lines on the GPU with the nested interior solves and the interface right-hand side
-        as HIP kernels (sem_amd/csrc/ns_condense.hip): 3 + 1 + CR + 3 launches, no gathers or copies."""
+    def _iface_solve_T(self, g):
+        """The transposed interface system S^T x_B = g (g is not modified)."""
+        if self.sweep == "cr":
+            return self._cr_solve_T(g)
+        if getattr(self, "_tw", None) is not None:
+            return twisted_thomas_solve_T(self._tw, g)
+        if getattr(self, "_th", None) is not None:
+            return fused_thomas_solve_T(*self._th, g)
+        return plain_thomas_solve_T(self.Dinv, self.S_lo, self.Uh, g)
+
+    # ------------------------------------------------------------------ the four condensation steps
+    # With the lines split into column interiors I and interface lines B, both directions run
+    #     y_I = A_II^-1 b_I,   g = b_B - A_BI y_I,   S x_B = g,   x_I = A_II^-1 (b_I - A_IB x_B);
+    # J^T x = b takes them with aIB and aBI in each other's place and every stored operator applied transposed
+    # (A_II^-T, S^T).  Each path -- the HIP kernels, the torch algebra -- has one body, which receives the
+    # direction's interior solve, interface solve and two line couplings.  A_IB and A_BI are diagonal per line, so
+    # the only transposed data kept are two permuted copies of those diagonals (2 (P-1) m doubles per column each), in
+    # each other's layout (_require_T).
+    def _condense_hip(self, B, nested, iface, a_g, a_I, prefix, coupled=False, own_rhs=None):
+        """The condensation steps on the GPU (sem_amd/csrc/ns_condense.hip, ns_condense_transpose.hip): 3 + 1 + sweep
+        + 3 launches, no gathers or copies.  nested: the library's nested interior solve (sem_nested_solve or
+        sem_nested_solve_t); iface: the interface solve; a_g: the line couplings of the interface right-hand side, in
+        aBI's layout [e, s, l, r]; a_I: those of the back substitution, in aIB's layout [e, l, s, r]; prefix names
+        the phases.  coupled (forward only, ABI 11): the interface right-hand side from the forward element step's
+        T = Xi b_i and the edge values, and the back substitution from the same work arrays and Xi A_iB, instead of
+        two nested solves through Xi.  own_rhs: the strip hook (_own_rhs).  The work arrays are shared by both
+        directions: a solver's solves are stream-ordered, not concurrent."""
         import ctypes as C
         from .. import _lib
         lib = _lib.load()
@@ -1284,128 +1311,110 @@ class VelocityJacobianSolver:
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         v = C.c_void_p
         b1 = B.data_ptr() + 8 * m   # line e P + 1: first interior line of column e
-        coupled = bool(d.XiB) and self.nested_back == "coupled"
-        with phase("vsolve.nested_fwd"):
-            if coupled:   # ABI 11: element and edge steps, then g from T and the edge values (no y_I formed)
+        coupled = coupled and bool(d.XiB)
+        with phase(prefix + ".nested_fwd"):
+            if coupled:   # element and edge steps, then g from T and the edge values (no y_I formed)
                 _lib.check(lib.sem_nested_iface_rhs(C.byref(d), v(b1), P * m, v(B.data_ptr()), m,
-                                                    v(self.aBI.data_ptr()), v(yI.data_ptr()), self.nI,
+                                                    v(a_g.data_ptr()), v(yI.data_ptr()), self.nI,
                                                     v(g.data_ptr()), st))
             else:
-                _lib.check(lib.sem_nested_solve(C.byref(d), v(b1), P * m, None, None, v(yI.data_ptr()), self.nI,
-                                                st))
-                _lib.check(lib.sem_interface_rhs(P, nex, m, v(B.data_ptr()), m, v(self.aBI.data_ptr()),
+                _lib.check(nested(C.byref(d), v(b1), P * m, None, None, v(yI.data_ptr()), self.nI, st))
+                _lib.check(lib.sem_interface_rhs(P, nex, m, v(B.data_ptr()), m, v(a_g.data_ptr()),
                                                  v(yI.data_ptr()), self.nI, v(g.data_ptr()), st))
-            self._own_rhs(g, B)
-        with phase("vsolve.iface_solve"):
-            xB = self._iface_solve(g)
+            if own_rhs is not None:
+                own_rhs(g, B)
+        with phase(prefix + ".iface_solve"):
+            xB = iface(g)
         out = torch.empty((NX, m), dtype=torch.float64, device=self.device)
         out[0::P] = xB
-        # back substitution x_I = A_II^-1 (b_I - A_IB x_B): by default from the forward solve's work arrays and
-        # Xi A_iB (ABI 11; nested_back = "full" re-solves with Xi, the ABI-10 path, for A/B)
-        back = lib.sem_nested_back_solve if coupled else lib.sem_nested_solve
-        with phase("vsolve.nested_back"):
-            _lib.check(back(C.byref(d), v(b1), P * m, v(self.aIB.data_ptr()), v(xB.data_ptr()),
+        # back substitution x_I = A_II^-1 (b_I - A_IB x_B): a second nested solve, or the coupled form
+        back = lib.sem_nested_back_solve if coupled else nested
+        with phase(prefix + ".nested_back"):
+            _lib.check(back(C.byref(d), v(b1), P * m, v(a_I.data_ptr()), v(xB.data_ptr()),
                             v(out.data_ptr() + 8 * m), P * m, st))
         return out
 
-    # ------------------------------------------------------------------ iterative refinement
-    def set_operator(self, apply_lines, amax=None, apply_lines_T=None):
-        """apply_lines(X) -> J X on (NX, m) line arrays (the matrix-free Jacobian apply of the solver that owns
-        this factor); amax(t) -> max |t| over every part (a partitioned solve reduces over the ranks);
-        apply_lines_T(X) -> J^T X is the operator of check_refinement_T and of the transposed solve's refinement."""
-        self._apply = apply_lines
-        self._apply_T = apply_lines_T
-        self._amax = amax if amax is not None else (lambda t: float(t.abs().max()))
-
-    def check_refinement(self, tau=None, seed=17):
-        """Measure the factor's normwise backward error eta = ||J x - b|| / (||J|| ||x|| + ||b||) (max norms) on a
-        seeded probe, ||J|| estimated from below by ||J s|| for a random sign vector s (so eta is over-estimated),
-        and turn on one refinement step per solve when eta > tau (SEM_REFINE_ETA, default 1e-13; 0 refines
-        always, inf never).  Every part of a partitioned solve takes the same decisions (reduced norms).  A
-        non-finite eta (a singular or overflowing factor block) raises RuntimeError instead of passing as "no
-        refinement needed" (max(0, nan) is 0).  Returns eta."""
-        if self._apply is None:
-            raise RuntimeError("set_operator() first")
-        if tau is None:
-            tau = float(os.environ.get("SEM_REFINE_ETA", "1e-13"))
-        # probe vectors drawn over the GLOBAL lines and sliced: on a partition, a shared line's entries must be equal
-        # on both ranks (the strip solve's contract); per-rank draws made them differ and the residual of the
-        # inconsistent right-hand side read as a backward error of 1e-4 at cfg5 (a false refinement)
-        l0, l1, NXg = self._probe_lines()
-        g = torch.Generator(device=self.device).manual_seed(seed)
-        b = (torch.rand((NXg, self.m), dtype=torch.float64, device=self.device, generator=g) * 2 - 1)[l0:l1].contiguous()
-        sgn = torch.sign(torch.rand((NXg, self.m), dtype=torch.float64, device=self.device, generator=g)
-                         - 0.5)[l0:l1].contiguous()
-        self.refine = False
-        nJ = self._amax(self._apply(sgn))
-        probes = {0: b}
-
-        def probe(k):   # probe k: right-hand side k (0: the one above; more drawn on demand, same generator)
-            if k not in probes:
-                probes[k] = (torch.rand((NXg, self.m), dtype=torch.float64, device=self.device, generator=g) * 2
-                             - 1)[l0:l1].contiguous()
-            bk = probes[k]
-            x = self._solve_lines(bk)
-            return self._amax(bk - self._apply(x)) / (nJ * self._amax(x) + self._amax(bk))
-
-        eta = probe(0)
-        if not math.isfinite(eta):
-            raise RuntimeError(f"velocity factor: non-finite backward error on the probe ({eta}): a singular or "
-                               "overflowing pivot block")
-        self.refine_eta = eta
-        self.refine = eta > tau
-        return eta
-
-    def _probe_lines(self):
-        """(first, end, count) of this solver's lines among all lines of the mesh: the whole mesh here."""
-        return 0, self.NX, self.NX
-
-    def _solve_lines(self, B):
-        """x = J^-1 b with b, x as (NX, 2 NY) line arrays (every line: u then v); with `refine` set, one step of
-        iterative refinement on the matrix-free Jacobian apply."""
-        X = self._solve_lines_once(B)
-        if self.refine:
-            X = X + self._solve_lines_once(B - self._apply(X))
-        return X
-
-    def _solve_lines_once(self, B):
+    def _condense_torch(self, B, interior, iface, c_g, c_I, back=None, own_rhs=None):
+        """The condensation steps in torch, on any device.  interior(R): the column-interior solve of R (columns, nI,
+        k); iface(g): the interface solve; c_g, c_I: the line couplings that form the interface right-hand side and
+        the back substitution's, each the pair of its (nex, P-1, m) views for the interface lines e and e + 1 of
+        column e (_line_couplings; None at P = 1).  back(yI, xB) replaces the second interior solve (the dense
+        interiors keep W = A_II^-1 A_IB); own_rhs: the strip hook (_own_rhs)."""
         P, nex, m, NX = self.P, self.nex, self.m, self.NX
-        if (self.device.type == "cuda" and P > 1 and self.interior == "nested"
-                and getattr(self, "hip_nested", True)):
-            return self._solve_lines_hip(B)
         g = B[0::P].clone()                                    # interface lines (nex+1, m)
         if P > 1:
             bI = B[:-1].reshape(nex, P, m)[:, 1:, :].reshape(nex, self.nI, 1)
-            if self.interior == "nested":
-                yI = self._nested_solve(bI)
-            elif self.interior == "inverse":
-                yI = torch.bmm(self.Ainv, bI)
-            else:
-                yI = torch.linalg.lu_solve(self.LU, self.piv, bI)
+            yI = interior(bI)
             yIr = yI.view(nex, P - 1, m)
-            g[:-1] -= (self.aBI[:, 0] * yIr).sum(1)
-            g[1:] -= (self.aBI[:, 1] * yIr).sum(1)
-        self._own_rhs(g, B)
-        xB = self._iface_solve(g)
+            g[:-1] -= (c_g[0] * yIr).sum(1)
+            g[1:] -= (c_g[1] * yIr).sum(1)
+        if own_rhs is not None:
+            own_rhs(g, B)
+        xB = iface(g)
         out = torch.empty((NX, m), dtype=torch.float64, device=self.device)
         out[0::P] = xB
         if P > 1:
-            if self.interior == "nested":   # x_I = A_II^-1 (b_I - A_IB x_B); A_IB is diagonal per line
-                rI = bI.view(nex, P - 1, m) - (self.aIB[:, :, 0, :] * xB[:-1, None, :]
-                                                + self.aIB[:, :, 1, :] * xB[1:, None, :])
-                xI = self._nested_solve(rI.reshape(nex, self.nI, 1))
+            if back is None:   # x_I = A_II^-1 (b_I - A_IB x_B); A_IB is diagonal per line
+                rI = bI.view(nex, P - 1, m) - (c_I[0] * xB[:-1, None, :] + c_I[1] * xB[1:, None, :])
+                xI = interior(rI.reshape(nex, self.nI, 1))
             else:
-                xI = yI.view(nex, self.nI) - (torch.bmm(self.W[:, :, 0, :], xB[:-1, :, None])
-                                              + torch.bmm(self.W[:, :, 1, :], xB[1:, :, None]))[..., 0]
+                xI = back(yI, xB)
             out[:-1].view(nex, P, m)[:, 1:, :] = xI.view(nex, P - 1, m)
         return out
 
-    # ------------------------------------------------------------------ transposed solve (transpose=True)
-    # J^T x = b from the forward factor.  With the lines split into column interiors I and interface lines B,
-    #     y_I = A_II^-T b_I,   g = b_B - A_IB^T y_I,   S^T x_B = g,   x_I = A_II^-T (b_I - A_BI^T x_B):
-    # the forward solve's four steps with aIB and aBI in each other's place and every stored operator applied
-    # transposed.  A_IB and A_BI are diagonal per line, so the only transposed data kept are the two permuted copies
-    # of those diagonals (2 (P-1) m doubles per column each), in each other's layout.
+    def _line_couplings(self):
+        """(A_BI, A_IB), diagonal per line, each as the pair of its (nex, P-1, m) views for the interface lines e and
+        e + 1 of column e."""
+        if self.P == 1:
+            return None, None
+        return (self.aBI[:, 0], self.aBI[:, 1]), (self.aIB[:, :, 0, :], self.aIB[:, :, 1, :])
+
+    def _solve_lines_once(self, B):
+        if (self.device.type == "cuda" and self.P > 1 and self.interior == "nested"
+                and getattr(self, "hip_nested", True)):
+            return self._solve_lines_hip(B)
+        cBI, cIB = self._line_couplings()
+        if self.P == 1 or self.interior == "nested":
+            return self._condense_torch(B, self._nested_solve, self._iface_solve, cBI, cIB, own_rhs=self._own_rhs)
+        if self.interior == "inverse":
+            interior = lambda R: torch.bmm(self.Ainv, R)                          # noqa: E731
+        else:
+            interior = lambda R: torch.linalg.lu_solve(self.LU, self.piv, R)      # noqa: E731
+
+        def back(yI, xB):   # x_I = y_I - W x_B with W = A_II^-1 A_IB
+            return yI.view(self.nex, self.nI) - (torch.bmm(self.W[:, :, 0, :], xB[:-1, :, None])
+                                                 + torch.bmm(self.W[:, :, 1, :], xB[1:, :, None]))[..., 0]
+        return self._condense_torch(B, interior, self._iface_solve, cBI, cIB, back, self._own_rhs)
+
+    def _solve_lines_hip(self, B):
+        """_solve_lines_once on the GPU.  nested_back = "full" re-solves with Xi in the back substitution (the ABI-10
+        path, for A/B) instead of the coupled form."""
+        from .. import _lib
+        return self._condense_hip(B, _lib.load().sem_nested_solve, self._iface_solve, self.aBI, self.aIB, "vsolve",
+                                  coupled=self.nested_back == "coupled", own_rhs=self._own_rhs)
+
+    def _solve_lines_once_T(self, B):
+        self._require_T()
+        if (self.device.type == "cuda" and self.P > 1 and self._edge_thomas and self._ne1 <= 32
+                and getattr(self, "hip_nested", True)):
+            return self._solve_lines_hip_T(B)   # (a factor on the dense edge inverse takes the torch path below)
+        cBI, cIB = self._line_couplings()
+        return self._condense_torch(B, self._nested_solve_T, self._iface_solve_T, cIB, cBI)
+
+    def _solve_lines_hip_T(self, B):
+        """_solve_lines_once_T on the GPU: the "full" path of the forward solve with sem_nested_solve_t
+        (ns_condense_transpose.hip), the permuted couplings and the transposed interface sweep."""
+        from .. import _lib
+        return self._condense_hip(B, _lib.load().sem_nested_solve_t, self._iface_solve_T, self._aIBp, self._aBIp,
+                                  "vsolve_T")
+
+    # ------------------------------------------------------------------ the solve driver
+    # One implementation per entry point for both directions, named by the suffix s: "" for J x = b, "_T" for
+    # J^T x = b.  A direction's state is the attribute twins refine / refine_T, refine_eta / refine_eta_T, _apply /
+    # _apply_T, _graph / _graph_T, _bin / _bin_T and _xout / _xout_T, its line solve _solve_lines_once /
+    # _solve_lines_once_T: the driver reaches them by the suffix, and the public methods below it are its wrappers.
+    # A subclass supplies the line solves and _require_T, the one check of whether it serves the transposed
+    # direction; the driver is inherited.
     def _require_T(self):
         if not self.transpose:
             raise NotImplementedError("the line-condensation velocity solve serves no transposed solve unless it is "
@@ -1417,135 +1426,107 @@ class VelocityJacobianSolver:
             self._aIBp = self.aIB.permute(0, 2, 1, 3).contiguous()      # aIB in aBI's layout: [e, s, l, r]
             self._aBIp = self.aBI.permute(0, 2, 1, 3).contiguous()      # aBI in aIB's layout: [e, l, s, r]
 
-    def _iface_solve_T(self, g):
-        """The transposed interface system S^T x_B = g (g is not modified)."""
-        if self.sweep == "cr":
-            return self._cr_solve_T(g)
-        if getattr(self, "_tw", None) is not None:
-            return twisted_thomas_solve_T(self._tw, g)
-        if getattr(self, "_th", None) is not None:
-            return fused_thomas_solve_T(*self._th, g)
-        return plain_thomas_solve_T(self.Dinv, self.S_lo, self.Uh, g)
+    def _require(self, s):
+        if s:
+            self._require_T()
+        elif not self.factored:
+            raise RuntimeError("factor() first")
 
-    def _solve_lines_hip_T(self, B):
-        """_solve_lines_once_T on the GPU: sem_nested_solve_t (ns_condense_transpose.hip), sem_interface_rhs with
-        the permuted aIB, the transposed interface sweep, sem_nested_solve_t with the permuted aBI and x_B.  The
-        "full" path of the forward solve (two nested solves through Xi); the work arrays are the forward solve's."""
-        import ctypes as C
-        from .. import _lib
-        lib = _lib.load()
-        P, nex, m, NX = self.P, self.nex, self.m, self.NX
-        if not (B.is_contiguous() and tuple(B.shape) == (NX, m) and B.dtype == torch.float64):
-            raise ValueError("line array must be a contiguous float64 (NX, m) tensor")
-        d = self._hip_nested()
-        _, _, _, yI, g, _ = self._work
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        v = C.c_void_p
-        b1 = B.data_ptr() + 8 * m   # line e P + 1: first interior line of column e
-        with phase("vsolve_T.nested_fwd"):
-            _lib.check(lib.sem_nested_solve_t(C.byref(d), v(b1), P * m, None, None, v(yI.data_ptr()), self.nI, st))
-            _lib.check(lib.sem_interface_rhs(P, nex, m, v(B.data_ptr()), m, v(self._aIBp.data_ptr()),
-                                             v(yI.data_ptr()), self.nI, v(g.data_ptr()), st))
-        with phase("vsolve_T.iface_solve"):
-            xB = self._iface_solve_T(g)
-        out = torch.empty((NX, m), dtype=torch.float64, device=self.device)
-        out[0::P] = xB
-        with phase("vsolve_T.nested_back"):
-            _lib.check(lib.sem_nested_solve_t(C.byref(d), v(b1), P * m, v(self._aBIp.data_ptr()), v(xB.data_ptr()),
-                                              v(out.data_ptr() + 8 * m), P * m, st))
-        return out
+    def set_operator(self, apply_lines, amax=None, apply_lines_T=None):
+        """apply_lines(X) -> J X on (NX, m) line arrays (the matrix-free Jacobian apply of the solver that owns
+        this factor); amax(t) -> max |t| over every part (a partitioned solve reduces over the ranks);
+        apply_lines_T(X) -> J^T X is the operator of check_refinement_T and of the transposed solve's refinement."""
+        self._apply = apply_lines
+        self._apply_T = apply_lines_T
+        self._amax = amax if amax is not None else (lambda t: float(t.abs().max()))
 
-    def _solve_lines_once_T(self, B):
-        self._require_T()
-        P, nex, m, NX = self.P, self.nex, self.m, self.NX
-        if (self.device.type == "cuda" and P > 1 and self._edge_thomas and self._ne1 <= 32
-                and getattr(self, "hip_nested", True)):
-            return self._solve_lines_hip_T(B)   # (a factor on the dense edge inverse takes the torch path below)
-        g = B[0::P].clone()                                    # interface lines (nex+1, m)
-        if P > 1:
-            bI = B[:-1].reshape(nex, P, m)[:, 1:, :].reshape(nex, self.nI, 1)
-            yIr = self._nested_solve_T(bI).view(nex, P - 1, m)
-            g[:-1] -= (self.aIB[:, :, 0] * yIr).sum(1)
-            g[1:] -= (self.aIB[:, :, 1] * yIr).sum(1)
-        xB = self._iface_solve_T(g)
-        out = torch.empty((NX, m), dtype=torch.float64, device=self.device)
-        out[0::P] = xB
-        if P > 1:   # x_I = A_II^-T (b_I - A_BI^T x_B); A_BI is diagonal per line
-            rI = bI.view(nex, P - 1, m) - (self.aBI[:, 0] * xB[:-1, None, :] + self.aBI[:, 1] * xB[1:, None, :])
-            xI = self._nested_solve_T(rI.reshape(nex, self.nI, 1))
-            out[:-1].view(nex, P, m)[:, 1:, :] = xI.view(nex, P - 1, m)
-        return out
+    def _probe_lines(self):
+        """(first, end, count) of this solver's lines among all lines of the mesh: the whole mesh here."""
+        return 0, self.NX, self.NX
 
-    def _solve_lines_T(self, B):
-        """x = J^-T b with b, x as (NX, ncomp NY) line arrays; with `refine_T` set, one step of iterative refinement
-        on the transposed matrix-free apply (set_operator's apply_lines_T)."""
-        X = self._solve_lines_once_T(B)
-        if self.refine_T:
-            if self._apply_T is None:
-                raise RuntimeError("refine_T is set but no transposed operator: set_operator(..., apply_lines_T=...)")
-            X = X + self._solve_lines_once_T(B - self._apply_T(X))
+    def _refined(self, B, s):
+        """One line solve of direction s ("" or "_T"); with the direction's refine flag set, one step of iterative
+        refinement on its matrix-free apply."""
+        once = getattr(self, "_solve_lines_once" + s)
+        X = once(B)
+        if getattr(self, "refine" + s):
+            apply = getattr(self, "_apply" + s)
+            if apply is None:
+                raise RuntimeError(f"refine{s} is set but the direction has no operator: set_operator(...)")
+            X = X + once(B - apply(X))
         return X
 
-    def check_refinement_T(self, tau=None, seed=17):
-        """check_refinement for the transposed solve: eta = ||J^T x - b|| / (||J^T|| ||x|| + ||b||) on a seeded probe
-        (||J^T|| from below by ||J^T s|| for a random sign vector), refine_T = eta > tau (SEM_REFINE_ETA, default
-        1e-13), refine_eta_T = eta; a non-finite eta raises.  Returns eta."""
-        self._require_T()
-        if self._apply_T is None:
-            raise RuntimeError("set_operator(..., apply_lines_T=...) first")
+    def _gate(self, s, tau, seed):
+        """Measure the factor's normwise backward error eta = ||A x - b|| / (||A|| ||x|| + ||b||) (max norms; A = J,
+        or J^T for s = "_T") on a seeded probe, ||A|| estimated from below by ||A sgn|| for a random sign vector (so
+        eta is over-estimated), and turn on one refinement step per solve of that direction when eta > tau
+        (SEM_REFINE_ETA, default 1e-13; 0 refines always, inf never).  Every part of a partitioned solve takes the
+        same decisions (reduced norms).  A non-finite eta (a singular or overflowing factor block) raises RuntimeError
+        instead of passing as "no refinement needed" (max(0, nan) is 0).  Returns eta."""
+        apply = getattr(self, "_apply" + s)
+        if apply is None:
+            raise RuntimeError("set_operator(..., apply_lines_T=...) first" if s else "set_operator() first")
         if tau is None:
             tau = float(os.environ.get("SEM_REFINE_ETA", "1e-13"))
-        amax = self._amax if self._amax is not None else (lambda t: float(t.abs().max()))
+        # probe vectors drawn over the GLOBAL lines and sliced: on a partition, a shared line's entries must be equal
+        # on both ranks (the strip solve's contract); per-rank draws made them differ and the residual of the
+        # inconsistent right-hand side read as a backward error of 1e-4 at cfg5 (a false refinement)
+        l0, l1, NXg = self._probe_lines()
         g = torch.Generator(device=self.device).manual_seed(seed)
-        b = torch.rand((self.NX, self.m), dtype=torch.float64, device=self.device, generator=g) * 2 - 1
-        sgn = torch.sign(torch.rand((self.NX, self.m), dtype=torch.float64, device=self.device, generator=g) - 0.5)
-        self.refine_T = False
-        nJ = amax(self._apply_T(sgn))
-        x = self._solve_lines_T(b)
-        eta = amax(b - self._apply_T(x)) / (nJ * amax(x) + amax(b))
+        b = (torch.rand((NXg, self.m), dtype=torch.float64, device=self.device, generator=g) * 2 - 1)[l0:l1].contiguous()
+        sgn = torch.sign(torch.rand((NXg, self.m), dtype=torch.float64, device=self.device, generator=g)
+                         - 0.5)[l0:l1].contiguous()
+        setattr(self, "refine" + s, False)
+        amax = self._amax
+        nJ = amax(apply(sgn))
+        x = getattr(self, "_solve_lines" + s)(b)
+        eta = amax(b - apply(x)) / (nJ * amax(x) + amax(b))
         if not math.isfinite(eta):
-            raise RuntimeError(f"velocity factor: non-finite backward error of the transposed solve on the probe ({eta})")
-        self.refine_eta_T = eta
-        self.refine_T = eta > tau
+            raise RuntimeError(f"velocity factor: non-finite backward error on the probe ({eta}): a singular or "
+                               "overflowing pivot block")
+        setattr(self, "refine_eta" + s, eta)
+        setattr(self, "refine" + s, eta > tau)
         return eta
 
-    def capture_T(self):
-        """Capture the transposed solve in a hipGraph of its own, with its own input and output buffers (capture's
-        twin; solve_T / solve1_T replay it).  Forward and transposed solves of one solver share the nested solve's
-        work arrays: they are stream-ordered, not concurrent.  Returns False (the solve stays eager) off the GPU or
-        when the device libraries refuse the capture."""
-        self._require_T()
-        if self.device.type != "cuda":
-            return False
-        self._bin_T = torch.zeros((self.NX, self.m), dtype=torch.float64, device=self.device)
-        cur = torch.cuda.current_stream(self.device)
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(cur)
-        try:
-            with torch.cuda.stream(s):
-                self._solve_lines_T(self._bin_T)      # builds the tables and warms up outside the capture
-            cur.wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with no_gc(), torch.cuda.graph(g):
-                self._xout_T = self._solve_lines_T(self._bin_T)
-            self._graph_T = g
-            return True
-        except RuntimeError:
-            torch.cuda.synchronize(self.device)
-            self._graph_T = None
-            return False
+    def _capture(self, s):
+        """Capture the direction's line solve (refinement step included) in a hipGraph of its own, with its own input
+        and output buffers; False, and the solve stays eager, when the device libraries refuse the capture."""
+        b = torch.zeros((self.NX, self.m), dtype=torch.float64, device=self.device)
+        solve = getattr(self, "_solve_lines" + s)
+        setattr(self, "_bin" + s, b)
+        g, out = capture_graph(self.device, lambda: solve(b))
+        setattr(self, "_graph" + s, g)
+        setattr(self, "_xout" + s, out)
+        return g is not None
 
-    def solve1_T(self, b):
-        """x = A^-T b for a one-component operator (transpose=True); b is a length-N vector in the x-major numbering."""
-        self._require_T()
-        if self.ncomp != 1:
-            raise ValueError("solve1_T needs ncomp=1")
-        NX, NY = self.NX, self.NY
-        if self._graph_T is not None:
-            self._bin_T.copy_(b.reshape(NX, NY))
-            self._graph_T.replay()
-            return self._xout_T.reshape(-1).clone()
-        return self._solve_lines_T(b.reshape(NX, NY).clone()).reshape(-1)
+    def _solve_vectors(self, s, name, parts):
+        """The direction's solve of length-N vectors in the x-major numbering, one per component: packed into the line
+        layout, the direction's graph replayed when there is one (else the eager line solve), unpacked."""
+        self._require(s)
+        NX, NY, nc = self.NX, self.NY, len(parts)
+        if self.ncomp != nc:
+            raise ValueError(f"{name} needs ncomp={nc}" + (f"; use solve1{s}" if nc == 2 else ""))
+        graph = getattr(self, "_graph" + s)
+        if graph is not None:
+            b3 = getattr(self, "_bin" + s).view(NX, nc, NY)
+            for c, p in enumerate(parts):
+                b3[:, c, :] = p.reshape(NX, NY)
+            graph.replay()
+            out = getattr(self, "_xout" + s).view(NX, nc, NY)
+            return tuple(out[:, c, :].reshape(-1).clone() for c in range(nc))
+        B = torch.stack([p.reshape(NX, NY) for p in parts], dim=1).reshape(NX, self.m)
+        out = getattr(self, "_solve_lines" + s)(B).view(NX, nc, NY)
+        return tuple(out[:, c, :].reshape(-1) for c in range(nc))
+
+    # ---- J x = b
+    def _solve_lines(self, B):
+        """x = J^-1 b with b, x as (NX, ncomp NY) line arrays (every line: u then v); with `refine` set, one step of
+        iterative refinement on the matrix-free Jacobian apply."""
+        return self._refined(B, "")
+
+    def check_refinement(self, tau=None, seed=17):
+        """The backward-error gate of the forward solve (_gate): sets refine and refine_eta, returns eta."""
+        return self._gate("", tau, seed)
 
     def capture(self):
         """Capture the solve (about 3 (N_ex+1) + 10 launches) in a hipGraph: a Schur-complement
@@ -1555,70 +1536,36 @@ class VelocityJacobianSolver:
             return False
         if self.P > 1 and self.interior == "lu":
             return False   # the batched LU solve (rocSOLVER getrs) cannot be stream-captured
-        self._bin = torch.zeros((self.NX, self.m), dtype=torch.float64, device=self.device)
-        cur = torch.cuda.current_stream(self.device)
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(cur)
-        try:
-            with torch.cuda.stream(s):
-                self._solve_lines(self._bin)      # warm-up outside the capture (library workspaces)
-            cur.wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with no_gc(), torch.cuda.graph(g):
-                self._xout = self._solve_lines(self._bin)
-            self._graph = g
-            return True
-        except RuntimeError:
-            torch.cuda.synchronize(self.device)
-            self._graph = None
-            return False
-
-    def solve1(self, b):
-        """x = A^-1 b for a one-component operator; b is a length-N vector in the x-major numbering."""
-        if not self.factored:
-            raise RuntimeError("factor() first")
-        if self.ncomp != 1:
-            raise ValueError("solve1 needs ncomp=1")
-        NX, NY = self.NX, self.NY
-        if getattr(self, "_graph", None) is not None:
-            self._bin.copy_(b.reshape(NX, NY))
-            self._graph.replay()
-            return self._xout.reshape(-1).clone()
-        return self._solve_lines(b.reshape(NX, NY).clone()).reshape(-1)
-
-    def solve_T(self, bu, bv):
-        """(J^-T [bu; bv]) split as (xu, xv), for a solver built with transpose=True (the transposed condensation:
-        the nested interior solves and the interface sweep both run transposed, _solve_lines_once_T); otherwise
-        NotImplementedError."""
-        self._require_T()
-        if self.ncomp != 2:
-            raise ValueError("solve_T needs ncomp=2; use solve1_T")
-        NX, NY = self.NX, self.NY
-        if self._graph_T is not None:
-            b3 = self._bin_T.view(NX, 2, NY)
-            b3[:, 0, :] = bu.reshape(NX, NY)
-            b3[:, 1, :] = bv.reshape(NX, NY)
-            self._graph_T.replay()
-            out = self._xout_T.view(NX, 2, NY)
-            return out[:, 0, :].reshape(-1).clone(), out[:, 1, :].reshape(-1).clone()
-        B = torch.stack((bu.reshape(NX, NY), bv.reshape(NX, NY)), dim=1).reshape(NX, self.m)
-        out = self._solve_lines_T(B).view(NX, 2, NY)
-        return out[:, 0, :].reshape(-1), out[:, 1, :].reshape(-1)
+        return self._capture("")
 
     def solve(self, bu, bv):
         """(J^-1 [bu; bv]) split as (xu, xv); bu, bv are length-N vectors in the x-major numbering."""
-        if not self.factored:
-            raise RuntimeError("factor() first")
-        if self.ncomp != 2:
-            raise ValueError("solve needs ncomp=2; use solve1")
-        NX, NY = self.NX, self.NY
-        if getattr(self, "_graph", None) is not None:
-            b3 = self._bin.view(NX, 2, NY)
-            b3[:, 0, :] = bu.reshape(NX, NY)
-            b3[:, 1, :] = bv.reshape(NX, NY)
-            self._graph.replay()
-            out = self._xout.view(NX, 2, NY)
-            return out[:, 0, :].reshape(-1).clone(), out[:, 1, :].reshape(-1).clone()
-        B = torch.stack((bu.reshape(NX, NY), bv.reshape(NX, NY)), dim=1).reshape(NX, self.m)
-        out = self._solve_lines(B).view(NX, 2, NY)
-        return out[:, 0, :].reshape(-1), out[:, 1, :].reshape(-1)
+        return self._solve_vectors("", "solve", (bu, bv))
+
+    def solve1(self, b):
+        """x = A^-1 b for a one-component operator; b is a length-N vector in the x-major numbering."""
+        return self._solve_vectors("", "solve1", (b,))[0]
+
+    # ---- J^T x = b: _require_T refuses unless this solver serves it
+    def _solve_lines_T(self, B):
+        """x = J^-T b on line arrays; with `refine_T` set, one step of iterative refinement on the transposed
+        matrix-free apply (set_operator's apply_lines_T)."""
+        return self._refined(B, "_T")
+
+    def check_refinement_T(self, tau=None, seed=17):
+        """The backward-error gate of the transposed solve (_gate): sets refine_T and refine_eta_T, returns eta."""
+        self._require_T()
+        return self._gate("_T", tau, seed)
+
+    def capture_T(self):
+        """capture's twin: solve_T / solve1_T replay a graph of their own.  Returns False off the GPU."""
+        self._require_T()
+        return self.device.type == "cuda" and self._capture("_T")
+
+    def solve_T(self, bu, bv):
+        """(J^-T [bu; bv]) split as (xu, xv), from the forward factor."""
+        return self._solve_vectors("_T", "solve_T", (bu, bv))
+
+    def solve1_T(self, b):
+        """x = A^-T b for a one-component operator; b is a length-N vector in the x-major numbering."""
+        return self._solve_vectors("_T", "solve1_T", (b,))[0]
