@@ -93,8 +93,10 @@ class BoussinesqCoupler:
                 self._inner = DistributedInner(None, (off, cd._mesh.device), pns.dist, pns.group, segments=segs,
                                                backend_device=pns.backend_device())
         self.iterations = 0
-        self.timing = {k: 0.0 for k in ("residuals", "jacobian_apply", "cd_update", "ns_update")}
+        self.timing = {k: 0.0 for k in ("residuals", "jacobian_apply", "cd_update", "ns_update", "jacobian_apply_T",
+                                        "cd_update_T", "ns_update_T")}
         self.calls = {k: 0 for k in self.timing}
+        self.Re, self.Ra, self.Pr = Re, Ra, Pr   # the parameters of residual_partials (Pe = Re Pr, Gr = Ra / Pr)
 
     def _timed(self, key, fn, *a, **kw):
         t0 = time.perf_counter()
@@ -345,6 +347,169 @@ class BoussinesqCoupler:
             n_new = self._norm(r_new)
         return x_new, r_new, n_new
 
+    # ------------------------------------------------------------------ reverse mode (whole-mesh solvers)
+    # The coupled Jacobian at the linearisation, rows [rT | ru | rv | rp], columns [T | u | v | p]:
+    #     J = [ A_cd          J_Tu I_cd   J_Tv I_cd   0 ]      A_cd, J_Tu, J_Tv: cd._get_dresiduals
+    #         [ c_T M I_ns  (      the NS block A_ns      ) ]   A_ns, c_T M (rv rows): ns._get_dresiduals
+    # so J^T w sums each solver's transposed map with the other's coupling term carried back through the
+    # transposed mesh transfer.  Nothing below is reached from the forward solve.
+    def _own_solvers(self):
+        """The solvers whose maps this rank runs (both; one each in the parallel coupler)."""
+        return self.cd, self.ns
+
+    def _reverse_checks(self, what, linearized=False):
+        """The refusals of every reverse-mode method, before anything else runs (and before any collective): a
+        partitioned solver raises its own whole-mesh ValueError; with linearized, a solver that shows no
+        linearisation raises RuntimeError (a duck-typed solver without these attributes raises on its own)."""
+        for s in (self.cd, self.ns):
+            if getattr(s, "_part", None) is not None:
+                s._whole_mesh_only(f"BoussinesqCoupler.{what}")
+        if linearized:
+            for s in self._own_solvers():
+                for attr in ("_Jac_T_u", "_jac_kw"):
+                    if hasattr(s, attr) and getattr(s, attr) is None:
+                        raise RuntimeError(f"BoussinesqCoupler: residuals and linearize must run before {what}")
+
+    def _to_cd_T(self, f_cd_bar):
+        """The transpose of _to_cd: a CD-node vector carried back to the NS nodes."""
+        if self._same_mesh:
+            return f_cd_bar
+        from .components import transfer_T
+        return transfer_T(f_cd_bar, src=self.ns, dst=self.cd)
+
+    def _to_ns_T(self, f_ns_bar):
+        """The transpose of _to_ns: an NS-node vector carried back to the CD nodes."""
+        if self._same_mesh:
+            return f_ns_bar
+        from .components import transfer_T
+        return transfer_T(f_ns_bar, src=self.cd, dst=self.ns)
+
+    def jacobian_apply_T(self, w):
+        """apply_linear, rev mode: J^T w for the operator J of jacobian_apply at the current linearisation, so
+        that <jacobian_apply(dx), w> = <dx, jacobian_apply_T(w)>.  Two fused transposed launches
+        (cd._get_dresiduals_T, ns._get_dresiduals_T with the temperature bar) and three pointwise sums."""
+        self._reverse_checks("jacobian_apply_T")
+        if self._device and not isinstance(w, torch.Tensor):
+            return self._host_call(self.jacobian_apply_T, w)
+        wT, wu, wv, wp = self._split(w)
+        t0 = time.perf_counter()
+        aT, au, av = self.cd._get_dresiduals_T(wT)
+        bu, bv, bp, bT = self.ns._get_dresiduals_T(wu, wv, wp, want_T=True)
+        out = self._join(aT + self._to_ns_T(bT), bu + self._to_cd_T(au), bv + self._to_cd_T(av), bp)
+        self.timing["jacobian_apply_T"] += time.perf_counter() - t0
+        self.calls["jacobian_apply_T"] += 1
+        return out
+
+    def block_jacobi_T(self, r):
+        """The transpose of block_jacobi: each component's adjoint solve_linear on its own block
+        (cd._get_update_T, ns._get_update_T), zero initial guesses."""
+        self._reverse_checks("block_jacobi_T")
+        if self._device and not isinstance(r, torch.Tensor):
+            return self._host_call(self.block_jacobi_T, r)
+        rT, ru, rv, rp = self._split(r)
+        lT = self._timed("cd_update_T", self.cd._get_update_T, rT)
+        lu, lv, lp = self._timed("ns_update_T", self.ns._get_update_T, ru, rv, rp)
+        return self._join(lT, lu, lv, lp)
+
+    def solve_adjoint(self, g, lam0=None, maxiter=None):
+        """Solve J^T lam = g at the current linearisation: gmres_left on jacobian_apply_T, preconditioned by
+        block_jacobi_T, with _linear_jnk's tolerance (atol_gmres, rtol 0), restart, inner products and
+        restart-jump safeguard (both solvers' _mtol are restored afterwards); maxiter counts restarts and
+        defaults to _linear_jnk's 5000.  g and lam0 in the working form, or global NumPy vectors in device mode
+        (the result then is one too).  RuntimeError before linearize and when GMRES does not converge.
+
+        J must be regular: odd element counts in both directions and even P (with an even count the
+        equal-order Jacobian pinned at int(N / 2) is singular and a right-hand side outside range(J^T) cannot
+        reach atol_gmres; the solve then ends with its RuntimeError within maxiter)."""
+        self._reverse_checks("solve_adjoint", linearized=True)
+        host = self._device and not isinstance(g, torch.Tensor)
+        if self._device:
+            b = self.to_local(g)
+            x0 = None if lam0 is None else self.to_local(lam0)
+            mv, pc = self.jacobian_apply_T, self.block_jacobi_T
+        else:
+            b = torch.from_numpy(np.ascontiguousarray(g, dtype=np.float64))
+            x0 = None if lam0 is None else torch.from_numpy(np.ascontiguousarray(lam0, dtype=np.float64))
+            mv = lambda t: torch.from_numpy(self.jacobian_apply_T(t.numpy()))  # noqa: E731
+            pc = lambda t: torch.from_numpy(self.block_jacobi_T(t.numpy()))  # noqa: E731
+        it = [0]
+
+        def cb(presid):
+            it[0] += 1
+            self._log(f'  adjoint GMRES {it[0]} ; {presid}')
+
+        saved = [(s, s._mtol) for s in (self.cd, self.ns) if s is not None and hasattr(s, "_mtol")]
+        self._jumps = 0
+        try:
+            res = gmres_left(mv, b, x0=x0, atol=self.atol_gmres, rtol=0.0, restart=self.restart,
+                             maxiter=5000 if maxiter is None else maxiter, precond=pc, callback=cb,
+                             inner=self._inner, jump=self._tighten_blocks, jump_ratio=self.JUMP_RATIO)
+        finally:
+            for s, m in saved:
+                s._mtol = m
+        self.restart_jumps = getattr(self, "restart_jumps", 0) + getattr(res, "jumps", 0)   # unset on an early return
+        self.adjoint_iterations, self.adjoint_res_norm = res.iters, res.res_norm
+        if res.info != 0:
+            raise RuntimeError(f'adjoint GMRES failed to converge in {res.info} restarts')
+        if self._device:
+            return self.to_global(res.x) if host else res.x
+        return res.x.numpy()
+
+    def residual_partials(self, x, name):
+        """dR/d(name) at the state x for name in "Ra", "Re", "Pr", as a coupled vector (the working form, or
+        a global NumPy vector for one in device mode).  The coupler sets Pe = Re Pr and Gr / Re = Ra / (Pr Re)
+        (CDOracle.residuals, NSOracle.residuals state the two residuals), so with conv(f) = u o G_x f + v o G_y f:
+            Ra:  rv: -(1 / (Pr Re)) M T
+            Pr:  rT: Re conv(T)          rv: +(Ra / (Pr^2 Re)) M T
+            Re:  rT: Pr conv(T)   ru: conv(u)   rv: conv(v) + (Ra / (Pr Re^2)) M T
+        on the free rows; Dirichlet rows, the pressure rows and the pin do not depend on a parameter.  Each term
+        is one fused apply of the solver it belongs to (_operator); no linearisation is needed."""
+        if name not in ("Ra", "Re", "Pr"):
+            raise ValueError("residual_partials: name must be 'Ra', 'Re' or 'Pr'")
+        self._reverse_checks("residual_partials")
+        if self._device and not isinstance(x, torch.Tensor):
+            return self._host_call(lambda t: self.residual_partials(t, name), x)
+        T, u, v, _ = self._split(x)
+        Re, Ra, Pr = self.Re, self.Ra, self.Pr
+        cd, ns = self.cd, self.ns
+        z = self._zeros(self.Nns, getattr(self, "_nns_loc", 0))
+        rT, ru, rv = self._zeros(self.Ncd, getattr(self, "_ncd_loc", 0)), z, z
+        MT = lambda: ns._operator(self._to_ns(T), c_mass=1.0, free=True)  # noqa: E731
+        convT = lambda: cd._operator(T, cu=self._to_cd(u), cv=self._to_cd(v), free=True)  # noqa: E731
+        if name == "Ra":
+            rv = -(1.0 / (Pr * Re)) * MT()
+        elif name == "Pr":
+            rT = Re * convT()
+            rv = (Ra / (Pr * Pr * Re)) * MT()
+        else:
+            rT = Pr * convT()
+            ru = ns._operator(u, cu=u, cv=v, free=True)
+            rv = ns._operator(v, cu=u, cv=v, free=True) + (Ra / (Pr * Re * Re)) * MT()
+        return self._join(rT, ru, rv, z)
+
+    def total_derivatives(self, x, functionals, params=("Ra", "Re", "Pr")):
+        """Total derivatives dF/dp of functionals (sem_amd.solvers.functionals) with respect to the parameters
+        `params` at the converged state x (||residuals(x)|| <= atol_nonlin): the coupler is linearised at x
+        (residuals, then linearize), one adjoint solve J^T lam = dF/dx runs per functional, and
+            dF/dp = F.partial(p) - lam^T dR/dp.
+        Returns {(F.name, p): value}; the adjoints and their 2-norms stay in self.adjoints / self.adjoint_norms
+        (by functional name, in the form x came in)."""
+        self._reverse_checks("total_derivatives")
+        host = self._device and not isinstance(x, torch.Tensor)
+        xl = self.to_local(x) if host else x
+        self.residuals(xl)
+        self.linearize(xl)
+        dR = {p: self.residual_partials(xl, p) for p in params}
+        out, self.adjoints, self.adjoint_norms = {}, {}, {}
+        for F in functionals:
+            lam = self.solve_adjoint(F.gradient(self, xl))
+            self.adjoint_norms[F.name] = self._norm(lam)
+            self.adjoints[F.name] = self.to_global(lam) if host else lam
+            for p in params:
+                lr = torch.dot(lam, dR[p]).item() if self._device else float(np.dot(lam, dR[p]))
+                out[(F.name, p)] = F.partial(self, xl, p) - lr
+        return out
+
 
 def run(points_plot, L_x, L_y, Re=1.e3, Ra=1.e3, Pr=0.71, P_cd=4, N_ex_cd=8, N_ey_cd=8, P_ns=4, N_ex_ns=8, N_ey_ns=8,
         mode='JNK', mtol_nonlin=1e-9, AGi=8, AGr=0.8, AGc=0.2, mtol_gmres=1e-10, restart=20, mtol_internal=1e-13):
@@ -438,6 +603,45 @@ class ParallelBoussinesqCoupler(BoussinesqCoupler):
             d = self.cd._get_solution(self._to_cd(u), self._to_cd(v), T0=T)
         else:
             d = self._join(*self.ns._get_solution(self._to_ns(T), u0=u, v0=v, p0=p))
+        return self._share(d)
+
+    # ------------------------------------------------------------------ reverse mode
+    # Transposed, both ranks contribute to the T, u and v blocks (rank 0 the CD map's outputs, rank 1 the NS
+    # map's), so the blocks meet in an all-reduce of two full coupled vectors (_reduce) where the forward maps
+    # fill disjoint blocks (_share).  residual_partials, the functionals and the Krylov iteration are
+    # replicated: they need no linearisation and run identically on both ranks.
+    def _own_solvers(self):
+        return (self.cd,) if self.rank == 0 else (self.ns,)
+
+    def _reduce(self, full):
+        """The sum over both ranks of a full coupled vector."""
+        full = torch.as_tensor(np.asarray(full, dtype=np.float64)).clone()
+        if self.dist.get_backend(self.group) == "nccl":   # RCCL reduces device tensors
+            full = full.to(torch.device("cuda", torch.cuda.current_device()))
+        self.dist.all_reduce(full, group=self.group)
+        return full.cpu().numpy()
+
+    def jacobian_apply_T(self, w):
+        self._reverse_checks("jacobian_apply_T")
+        wT, wu, wv, wp = self._split(w)
+        t0 = time.perf_counter()
+        if self.rank == 0:
+            aT, au, av = self.cd._get_dresiduals_T(wT)
+            full = self._join(aT, self._to_cd_T(au), self._to_cd_T(av), np.zeros(self.Nns))
+        else:
+            bu, bv, bp, bT = self.ns._get_dresiduals_T(wu, wv, wp, want_T=True)
+            full = self._join(self._to_ns_T(bT), bu, bv, bp)
+        self.timing["jacobian_apply_T"] += time.perf_counter() - t0
+        self.calls["jacobian_apply_T"] += 1
+        return self._reduce(full)
+
+    def block_jacobi_T(self, r):
+        self._reverse_checks("block_jacobi_T")
+        rT, ru, rv, rp = self._split(r)
+        if self.rank == 0:
+            d = self._timed("cd_update_T", self.cd._get_update_T, rT)
+        else:
+            d = self._join(*self._timed("ns_update_T", self.ns._get_update_T, ru, rv, rp))
         return self._share(d)
 
 

@@ -219,6 +219,23 @@ class ConvectionDiffusionSolver:
             raise ValueError(f"ConvectionDiffusion: {what} is implemented for whole-mesh solvers only "
                              "(no transposed strip apply)")
 
+    def _operator(self, x, c_mass=0.0, c_stiff=0.0, cu=None, cv=None, free=False):
+        """(c_mass M + c_stiff K + diag(cu) G_x + diag(cv) G_y) x on this solver's mesh in one fused launch, no
+        row replaced; free=True zeroes the Dirichlet rows.  What the coupler's parameter partials and the
+        functionals (solvers/functionals.py) are built from.  NumPy in, NumPy out; device tensors likewise."""
+        self._whole_mesh_only("_operator")
+        kw = {}
+        if cu is not None:
+            kw.update(c_gradx=1.0, cu=self._dev(cu))
+        if cv is not None:
+            kw.update(c_grady=1.0, cv=self._dev(cv))
+        y = self._mesh.apply(self._dev(x), c_mass=c_mass, c_stiff=c_stiff, **kw)
+        if free:
+            if self._free is None:   # 1 - m on the device
+                self._free = self._mesh.to_device((~self._dir.mask_np).astype(np.float64))
+            y = self._free * y
+        return self._out(y, x)
+
     def _apply_T(self, w, y=None, **kw):
         """A_D^T w: one fused transposed launch of Sys with identity Dirichlet rows."""
         return self._mesh.apply_transpose(w, y, dir_mode=_lib.DIR_IDENTITY, **self._sys_kw(), **self._dir.kw(), **kw)

@@ -620,6 +620,23 @@ class NavierStokesSolver:
         du, dv = vs.solve(ru - b_u, rv - b_v)
         return self._out(du, dres_u), self._out(dv, dres_u), self._out(dp, dres_u)
 
+    def _operator(self, x, c_mass=0.0, c_stiff=0.0, cu=None, cv=None, free=False):
+        """(c_mass M + c_stiff K + diag(cu) G_x + diag(cv) G_y) x on this solver's mesh in one fused launch, no
+        row replaced; free=True zeroes the velocity Dirichlet rows.  What the coupler's parameter partials and the
+        functionals (solvers/functionals.py) are built from.  NumPy in, NumPy out; device tensors likewise."""
+        self._whole_mesh_only("_operator")
+        kw = {}
+        if cu is not None:
+            kw.update(c_gradx=1.0, cu=self._dev(cu))
+        if cv is not None:
+            kw.update(c_grady=1.0, cv=self._dev(cv))
+        y = self._mesh.apply(self._dev(x), c_mass=c_mass, c_stiff=c_stiff, **kw)
+        if free:
+            if getattr(self, "_free", None) is None:   # 1 - m on the device
+                self._free = self._mesh.to_device((~self._dir.mask_np).astype(np.float64))
+            y = self._free * y
+        return self._out(y, x)
+
     # ------------------------------------------------------------------ reverse mode (whole mesh)
     def _get_dresiduals_T(self, ru_bar, rv_bar, rc_bar, want_T=False):
         """Transpose of _get_dresiduals(du, dv, dp, dT): (du_bar, dv_bar, dp_bar) = A^T (ru_bar, rv_bar, rc_bar) for
