@@ -220,6 +220,32 @@ int sem_kernel_name(const sem_handle* h, int algo, char* buf, int len);
  * limit (n_local + (P + 1) N_y >= 2^28). */
 int sem_apply_transpose(sem_handle* h, const sem_apply_desc* d, const double* z, double* y, void* stream);
 
+/* The transposed apply of ANY handle and any element-position range (entry point added at ABI 15):
+ * y = A_s^T z + c_acc y_in, where A_s is the matrix sem_apply applies on this handle.  sem_apply_transpose stays
+ * the whole-mesh form with its refusals; on a whole-mesh handle without a range the two launch the same kernel
+ * with the same arguments (bitwise-equal results).  The descriptor reads as for sem_apply_transpose, plus
+ *   pos_begin, pos_end     as in sem_apply_desc: only the output lines of element positions [pos_begin, pos_end)
+ *                          of 0..ncols (ncols = ex_end - ex_begin, position ncols = the closing line) are written,
+ *                          every other entry of y is left untouched; 0, 0 = all positions.  Every written node is
+ *                          its full local row: ranged launches that cover all positions give bitwise the unranged y.
+ * Strip handles (ex_begin > 0 or ex_end < nex).  The forward partitioned apply is A = sum_s R_s^T A_s R_s (R_s: the
+ * restriction to strip s's lines), hence A^T z = sum_s R_s^T A_s^T R_s z: each strip applies A_s^T to its slice of z and
+ * the interface exchange of the forward step (sem_interface_pack / unpack around a sum, or the neighbour exchange)
+ * assembles the shared lines.  z must hold EQUAL values on a shared line in both strips that hold it.  A_s is
+ *   - on BOTH interface lines, the partial sums of the strip's own elements (mass, stiffness, gradients): the
+ *     boundary term of the transposed gradient, G_x^T = -G_x + B, sits on the strip's own first and last line,
+ *     and the interface parts cancel in the exchange;
+ *   - on the right interface line (ex_end < nex), which the strip on the right owns: without the diagonal term
+ *     c_extra * ea and, under SEM_DIR_IDENTITY, with all-zero rows for its Dirichlet nodes.  This strip therefore
+ *     forms z' = (1 - m) z there like everywhere but adds neither m z nor ea z' nor c_acc y_in on that line; the
+ *     right-hand owner, for which the line is its (owned) first line, writes all three.
+ * dir_sides: W and E act only where the strip touches the mesh boundary (ex_begin == 0, ex_end == nex); dir_mask
+ * is indexed from the strip's first line, as in sem_apply.
+ * SEM_EINVAL: as sem_apply_transpose, and a range outside [0, ncols + 1) or with pos_begin >= pos_end.
+ * SEM_EUNSUPPORTED: an algo other than SEM_ALGO_AUTO, P outside the compiled range, n_local + (P + 1) N_y >= 2^28.
+ * y is not written when a status is returned. */
+int sem_apply_transpose_part(sem_handle* h, const sem_apply_desc* d, const double* z, double* y, void* stream);
+
 /* Name of the kernel sem_apply_transpose launches for this handle (for profiles / reports). */
 int sem_transpose_kernel_name(const sem_handle* h, char* buf, int len);
 

@@ -114,6 +114,7 @@ _SIGS = {
     "sem_apply": (C.c_int, [C.c_void_p, C.POINTER(SemApplyDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "sem_kernel_name": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int]),
     "sem_apply_transpose": (C.c_int, [C.c_void_p, C.POINTER(SemApplyDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sem_apply_transpose_part": (C.c_int, [C.c_void_p, C.POINTER(SemApplyDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "sem_transpose_kernel_name": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "sem_gather_elements": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sem_dss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,4 +1,4 @@
-// Apply-kernel selection: which kernel sem_apply / sem_apply_transpose run for a handle, an algo, an
+// Apply-kernel selection: which kernel sem_apply / sem_apply_transpose(_part) run for a handle, an algo, an
 // element-position range and the tuning knobs, the tile shapes and thresholds that decision rests on, and the
 // kernel names reported for it.  Pure host functions of plain values (no HIP header): sem_ops.hip, the band
 // and transposed launchers and tests/host/apply_select_main.cpp all read the policy from here.
@@ -111,6 +111,18 @@ inline ApplyChoice select_apply_transpose(const ApplyMesh& m, int algo, int pos_
   if (m.ex_begin != 0 || m.ex_end != m.nex)
     return refused(SEM_EUNSUPPORTED, "the transposed apply is implemented for whole-mesh handles only");
   if (pos_end != 0) return refused(SEM_EUNSUPPORTED, "the transposed apply has no element-position ranges");
+  if (algo != SEM_ALGO_AUTO) return refused(SEM_EUNSUPPORTED, "the transposed apply has one kernel (SEM_ALGO_AUTO)");
+  if (m.P < 1 || m.P > max_order) return refused(SEM_EUNSUPPORTED, "polynomial order outside compiled range");
+  if (!band_fits(m)) return refused(SEM_EUNSUPPORTED, "the transposed apply needs n_local + (P+1) N_y < 2^28");
+  return chosen(ApplyKind::Transpose);
+}
+
+// sem_apply_transpose_part: the same kernel on any handle (a strip applies its own A_s^T) and any
+// element-position range of it; pos_begin = pos_end = 0 gives all positions.
+inline ApplyChoice select_apply_transpose_part(const ApplyMesh& m, int algo, int pos_begin, int pos_end, int max_order) {
+  const bool ranged = pos_begin != 0 || pos_end != 0;
+  if (ranged && (pos_begin < 0 || pos_begin >= pos_end || pos_end > m.ex_end - m.ex_begin + 1))
+    return refused(SEM_EINVAL, "element-position range outside [0, ex_end - ex_begin + 1)");
   if (algo != SEM_ALGO_AUTO) return refused(SEM_EUNSUPPORTED, "the transposed apply has one kernel (SEM_ALGO_AUTO)");
   if (m.P < 1 || m.P > max_order) return refused(SEM_EUNSUPPORTED, "polynomial order outside compiled range");
   if (!band_fits(m)) return refused(SEM_EUNSUPPORTED, "the transposed apply needs n_local + (P+1) N_y < 2^28");

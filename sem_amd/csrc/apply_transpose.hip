@@ -22,7 +22,21 @@
 //   Y waves    lane = (line, element position), wave = column split: the same along y with cv z';
 // and every wave runs the epilogue of its nodes.  All coefficients are compile-time constants
 // (gll_consts.h), every sum has a fixed order, there are no atomics: results are bitwise
-// reproducible.  Whole-mesh handles only.
+// reproducible.
+//
+// Strips (sem_apply_transpose_part).  The matrix A_s that sem_apply applies on a strip handle is the operator
+// of the sub-mesh of the strip's own columns with the owner rule on its right interface line, so the kernel
+// runs on strip-local geometry: nex, NX, every gx and the mask index count from the strip's first line, the
+// 1-D weights and the boundary term b_x of the transposed gradient sit on the STRIP's first and last line
+// (the interface parts cancel in the exchange), and the W / E side bits reach the kernel only where the strip
+// touches the mesh boundary.  On a right interface line z' = (1 - m) z is formed as everywhere -- a Dirichlet
+// row of A_s is all zero there -- and m z, the diagonal term and the accumulate term are left to the right-hand
+// owner at no cost per node: the buffer resources of the two pointwise operands end before that line (nown
+// bytes: loads past them return 0), and the tiles that hold the line clear its Zo row between the barriers.
+// A launch covers element positions [pos0, pos1) of 0..nex (nex = the ghost position of the closing line);
+// tile tx starts at position pos0 + tx TXE.  A node's sums do not depend on where its tile starts, so ranged
+// launches that cover every position give bitwise the unranged result.  The strip / range code is the PART = true
+// instantiation; the whole-mesh launch without a range runs PART = false, the code it ran before strips existed.
 #include <hip/hip_runtime.h>
 
 #include "apply_common.h"
@@ -62,8 +76,10 @@ struct TArgs {
   const double* ea;
   const uint8_t* mask;
   double fKx, fKy, fM, fX, fY, cE, cA;  // cK dy/dx, cK dx/dy, cM dx dy/4, cX dy/2, cY dx/2
-  int NY, NX, nex, ney, tiles_y, nblk, nbytes, dir_mode, cpol;
+  int NY, NX, nex, ney, tiles_y, nblk, nbytes, dir_mode, cpol;  // NX, nex: the handle's own lines / columns
   unsigned sides;
+  int pos0, pos1;  // element positions of the launch
+  int nown;        // bytes of the lines whose pointwise terms this handle writes (nbytes, or one line less)
 };
 
 // GLL weights of order P as a device table (ws[] in LDS is filled from it)
@@ -104,7 +120,11 @@ __device__ __forceinline__ void trows(const double (&t)[2 * P + 1], double fL, d
   });
 }
 
-template <int P>
+// PART = false: every position of a handle that owns its last line (pos0, pos1 and nown are not read: the code of
+// the whole-mesh launch); PART = true: a position range and / or a right interface line.  The axis exists because a
+// measurement asked for it: with the three values read on every launch the whole-mesh apply at 64^2, P = 8 sat
+// 0.9 % above the previous kernel's range in an alternated A/B (profiles/strip_adjoint/ab_summary.txt).
+template <int P, bool PART>
 __global__ __launch_bounds__((TCfg<P>::THREADS)) void apply_transpose(const TArgs a) {
   using C = TCfg<P>;
   constexpr int n = C::n, BX = C::BX, BY = C::BY, PT = C::PT, PY = C::PY, LW = C::LW, NS = C::NS;
@@ -124,7 +144,7 @@ __global__ __launch_bounds__((TCfg<P>::THREADS)) void apply_transpose(const TArg
   const int tx = L / tyn, ty = L - tx * tyn;
 
   const int NY = a.NY, NX = a.NX, nex = a.nex, ney = a.ney;
-  const int m0 = tx * TXE, m1 = min(m0 + TXE, nex + 1);
+  const int m0 = (PART ? a.pos0 : 0) + tx * TXE, m1 = min(m0 + TXE, PART ? a.pos1 : nex + 1);
   const int n0 = ty * TYE, n1 = min(n0 + TYE, ney + 1);
   const int gx0 = m0 * P, gy0 = n0 * P;
   const int rows_ok = (min(m1, nex) - m0) * P + (m1 > nex ? 1 : 0);
@@ -141,7 +161,9 @@ __global__ __launch_bounds__((TCfg<P>::THREADS)) void apply_transpose(const TArg
   // [0, nbytes): absent operands and absent nodes need no branch
   const auto rz = brsrc(a.z, nbytes), ru = brsrc(a.cu, has_u ? nbytes : 0), rv = brsrc(a.cv, has_v ? nbytes : 0);
   const auto rm = brsrc(a.mask, has_m ? nbytes / 8 : 0);
-  const auto re = brsrc(a.ea, has_e ? nbytes : 0), ra = brsrc(a.y, has_a ? nbytes : 0);
+  // the pointwise operands end where the owned lines end: loads on a right interface line return 0 (y_in is not read)
+  const int nown = PART ? a.nown : nbytes;
+  const auto re = brsrc(a.ea, has_e ? nown : 0), ra = brsrc(a.y, has_a ? nown : 0);
   const auto ry = brsrc(a.y, nbytes);
 
   const double wsv = tid < n ? kTransposeW<P>.v[tid] : 0.0;
@@ -196,6 +218,13 @@ __global__ __launch_bounds__((TCfg<P>::THREADS)) void apply_transpose(const TArg
   }
   if (tid < n) ws[tid] = wsv;
   __syncthreads();
+  // a right interface line's m z entries are its owner's: cleared here, between the barriers, in the strip tiles
+  // that hold that line (the roles below do not touch Zo; the epilogue reads it behind the second barrier)
+  if constexpr (PART) {
+    if (nown != nbytes && m1 > nex) {
+      for (int c = tid; c < BY; c += C::THREADS) Zo[(rows_ok - 1) * PY + c] = 0.0;
+    }
+  }
 
   constexpr double w0 = GllConst<P>::w[0], wP = GllConst<P>::w[P];
   if (w < C::NXW) {
@@ -321,7 +350,11 @@ __global__ __launch_bounds__((TCfg<P>::THREADS)) void apply_transpose(const TArg
 template <int P>
 static int launch_transpose(const ApplyArgs& g, const sem_handle* h, hipStream_t s) {
   using C = TCfg<P>;
-  const long long tiles_x = (h->nex + 1 + C::TXE - 1) / C::TXE;
+  const int ncols = h->ex_end - h->ex_begin;
+  // element positions [pos0, pos1) of 0..ncols (ncols = the ghost position of the closing line)
+  const bool ranged = g.pos1 > 0;
+  const int pos0 = ranged ? g.pos0 : 0, pos1 = ranged ? g.pos1 : ncols + 1;
+  const long long tiles_x = (pos1 - pos0 + C::TXE - 1) / C::TXE;
   const long long tiles_y = (h->ney + 1 + C::TYE - 1) / C::TYE;
   const long long nblk = tiles_x * tiles_y;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return set_error(SEM_EINVAL, "mesh too large for one launch");
@@ -340,16 +373,23 @@ static int launch_transpose(const ApplyArgs& g, const sem_handle* h, hipStream_t
   t.cE = g.cE;
   t.cA = g.cA;
   t.NY = static_cast<int>(g.NY);
-  t.NX = static_cast<int>(g.NXg);
-  t.nex = g.nex;
+  t.NX = static_cast<int>(g.line_end - g.line_begin + 1);
+  t.nex = ncols;
   t.ney = g.ney;
   t.tiles_y = static_cast<int>(tiles_y);
   t.nblk = static_cast<int>(nblk);
   t.nbytes = g.n_local32 * 8;
   t.dir_mode = g.dir_mode;
   t.cpol = transpose_cpol(g.n_local32);
-  t.sides = g.sides;
-  hipLaunchKernelGGL((apply_transpose<P>), dim3(static_cast<unsigned>(nblk)), dim3(C::THREADS), 0, s, t);
+  // W and E are mesh sides: a strip's first / last line is one only where the strip touches the boundary
+  t.sides = g.sides & ~((h->ex_begin != 0 ? SEM_SIDE_W : 0u) | (h->ex_end != h->nex ? SEM_SIDE_E : 0u));
+  t.pos0 = pos0;
+  t.pos1 = pos1;
+  t.nown = t.nbytes - (h->ex_end == h->nex ? 0 : t.NY * 8);
+  if (ranged || t.nown != t.nbytes)
+    hipLaunchKernelGGL((apply_transpose<P, true>), dim3(static_cast<unsigned>(nblk)), dim3(C::THREADS), 0, s, t);
+  else
+    hipLaunchKernelGGL((apply_transpose<P, false>), dim3(static_cast<unsigned>(nblk)), dim3(C::THREADS), 0, s, t);
   return hip_check(hipGetLastError(), "apply (transpose) launch");
 }
 

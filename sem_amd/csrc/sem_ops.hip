@@ -351,7 +351,8 @@ int sem_apply(sem_handle* h, const sem_apply_desc* d, const double* x, double* y
   }
 }
 
-int sem_apply_transpose(sem_handle* h, const sem_apply_desc* d, const double* z, double* y, void* stream) {
+// The argument checks sem_apply_transpose and sem_apply_transpose_part share (before the kernel selection).
+static int transpose_args(const sem_handle* h, const sem_apply_desc* d, const double* z, const double* y) {
   if (!h || !d) return set_error(SEM_EINVAL, "null handle or descriptor");
   if (!z || !y) return set_error(SEM_EINVAL, "null z or y");
   if (z == y) return set_error(SEM_EINVAL, "z and y must not alias");
@@ -359,11 +360,28 @@ int sem_apply_transpose(sem_handle* h, const sem_apply_desc* d, const double* z,
     return set_error(SEM_EINVAL, "the transposed apply takes SEM_DIR_NONE or SEM_DIR_IDENTITY");
   if (d->eb || d->ec || d->ed) return set_error(SEM_EINVAL, "the transposed apply takes no eb / ec / ed (d = c_extra * ea)");
   if (d->dir_val) return set_error(SEM_EINVAL, "the transposed apply takes no dir_val");
+  return SEM_OK;
+}
+
+int sem_apply_transpose(sem_handle* h, const sem_apply_desc* d, const double* z, double* y, void* stream) {
+  if (int st = transpose_args(h, d, z, y)) return st;
   const ApplyChoice c = select_apply_transpose(mesh_of(h), d->algo, d->pos_end, kMaxOrder);
   if (c.status) return set_error(c.status, c.message);
   if (int st = on_device(h)) return st;
   ApplyArgs a = common_args(h, d, z, y);
   a.cE = d->ea ? d->c_extra : 0.0;
+  return launch_apply_transpose(a, h, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sem_apply_transpose_part(sem_handle* h, const sem_apply_desc* d, const double* z, double* y, void* stream) {
+  if (int st = transpose_args(h, d, z, y)) return st;
+  const ApplyChoice c = select_apply_transpose_part(mesh_of(h), d->algo, d->pos_begin, d->pos_end, kMaxOrder);
+  if (c.status) return set_error(c.status, c.message);
+  if (int st = on_device(h)) return st;
+  ApplyArgs a = common_args(h, d, z, y);
+  a.cE = d->ea ? d->c_extra : 0.0;
+  a.pos0 = d->pos_begin;
+  a.pos1 = d->pos_end;
   return launch_apply_transpose(a, h, reinterpret_cast<hipStream_t>(stream));
 }
 

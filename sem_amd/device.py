@@ -124,6 +124,32 @@ class Mesh:
         _lib.check(self._lib.sem_apply_transpose(self._h, C.byref(d), _ptr(z), _ptr(y), self.stream_ptr(stream)))
         return y
 
+    def apply_transpose_part(self, z, y=None, *, c_mass=0.0, c_stiff=0.0, c_gradx=0.0, c_grady=0.0, cu=None, cv=None,
+                             diag=None, c_acc=0.0, dir_mode=_lib.DIR_NONE, dir_mask=None, dir_sides=0, pos=None,
+                             stream=None, eb=None, ec=None, ed=None, dir_val=None, algo=_lib.ALGO_AUTO):
+        """Transposed apply of this handle's own matrix (include/sem_ops.h, sem_apply_transpose_part):
+        y = A_s^T z + c_acc y for the A_s that `apply` applies here -- on a strip the partial sums of its
+        own elements on both interface lines, the pointwise terms and Dirichlet entries of the right
+        interface line left to its right-hand owner -- so that summing the strips' results over the shared
+        lines (the forward exchange) gives the whole mesh's A_D^T z; z must agree on shared lines.
+        pos = (begin, end): write only the output lines of those element positions (0..ncols, ncols = the
+        closing line).  eb, ec, ed, dir_val and algo are refused as by apply_transpose."""
+        z = self._vec(z, "z")
+        if y is None:
+            y = torch.empty_like(z)
+        self._vec(y, "y")
+        for nm, t in (("cu", cu), ("cv", cv), ("diag", diag), ("eb", eb), ("ec", ec), ("ed", ed), ("dir_val", dir_val)):
+            self._vec(t, nm)
+        if dir_mask is not None:
+            if dir_mask.dtype != torch.uint8 or dir_mask.device != self.device or dir_mask.numel() != self.n_local:
+                raise ValueError("dir_mask must be a uint8 tensor of n_local entries on the mesh device")
+        d = _lib.SemApplyDesc(float(c_mass), float(c_stiff), float(c_gradx), float(c_grady), _ptr(cu), _ptr(cv),
+                              1.0 if diag is not None else 0.0, _ptr(diag), _ptr(eb), _ptr(ec), _ptr(ed), float(c_acc),
+                              int(dir_mode), _ptr(dir_mask), _ptr(dir_val), int(dir_sides), int(algo),
+                              *((0, 0) if pos is None else (int(pos[0]), int(pos[1]))))
+        _lib.check(self._lib.sem_apply_transpose_part(self._h, C.byref(d), _ptr(z), _ptr(y), self.stream_ptr(stream)))
+        return y
+
     def transpose_kernel_name(self):
         buf = C.create_string_buffer(128)
         _lib.check(self._lib.sem_transpose_kernel_name(self._h, buf, 128))

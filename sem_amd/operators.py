@@ -108,10 +108,13 @@ class SEMOperator:
 
     def apply_transpose(self, x, y=None, **kw):
         """Device apply of the transpose, A^T x, in one fused launch (sem_apply_transpose): x, y float64
-        tensors on the mesh device; kw = Dirichlet / accumulate options of Mesh.apply_transpose."""
+        tensors on the mesh device; kw = Dirichlet / accumulate options of Mesh.apply_transpose.  On a strip
+        mesh it is the strip's own A_s^T (Mesh.apply_transpose_part): partial sums on the interface lines,
+        as `apply` gives them, to be assembled by the interface exchange."""
         cX, cu, cY, cv, d = self._coeffs()
-        return self.mesh.apply_transpose(x, y, c_mass=self.cM, c_stiff=self.cK, c_gradx=cX, cu=cu, c_grady=cY, cv=cv,
-                                         diag=d, **kw)
+        m = self.mesh
+        launch = m.apply_transpose_part if (m.ex_begin != 0 or m.ex_end != m.nex) else m.apply_transpose
+        return launch(x, y, c_mass=self.cM, c_stiff=self.cK, c_gradx=cX, cu=cu, c_grady=cY, cv=cv, diag=d, **kw)
 
     def _mul_vec(self, x, apply):
         if isinstance(x, torch.Tensor):

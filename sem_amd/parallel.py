@@ -174,6 +174,39 @@ class StripApply:
         return self.exch.finish(y, work)
 
 
+class StripApplyT:
+    """One partitioned TRANSPOSED apply with the interface assembly: the twin of StripApply.
+
+    A = sum_s R_s^T A_s R_s gives A^T z = sum_s R_s^T A_s^T R_s z: every rank applies its strip's own A_s^T
+    (Mesh.apply_transpose_part) to its slice of z -- which must agree on shared lines, as an assembled
+    vector does -- and the forward step's exchange sums the partial results on the interface lines.  The
+    launch schedule is StripApply's: positions (0, 1) and (n, n + 1), exch.start, the interior (1, n),
+    exch.finish; one launch plus the exchange with overlap=False; a plain launch at world 1."""
+
+    def __init__(self, part, mesh, dist, group=None, kind="allreduce", overlap=True):
+        self.part, self.mesh, self.dist = part, mesh, dist
+        self.exch = part.exchanger(mesh, dist, group=group, kind=kind) if part.world > 1 else None
+        self.overlap = overlap and self.exch is not None
+        self.ncols = mesh.ex_end - mesh.ex_begin
+
+    def __call__(self, z, y=None, **kw):
+        m = self.mesh
+        if y is None:
+            y = torch.empty_like(z)
+        if self.exch is None:
+            return m.apply_transpose_part(z, y, **kw)
+        if not self.overlap:
+            m.apply_transpose_part(z, y, **kw)
+            return self.exch(y)
+        n = self.ncols
+        m.apply_transpose_part(z, y, pos=(0, 1), **kw)
+        m.apply_transpose_part(z, y, pos=(n, n + 1), **kw)
+        work = self.exch.start(y)
+        if n > 1:
+            m.apply_transpose_part(z, y, pos=(1, n), **kw)
+        return self.exch.finish(y, work)
+
+
 class DistributedInner:
     """Inner products of strip-partitioned vectors for sem_amd.krylov.gmres(inner=...).
 
@@ -248,6 +281,7 @@ class Partition:
             mesh = get_mesh(P, nex, ney, dx, dy, eb, ee)
         self.mesh = mesh
         self.step = StripApply(self.part, mesh, self.dist, self.group, self.exchange, self.overlap)
+        self.step_T = StripApplyT(self.part, mesh, self.dist, self.group, self.exchange, self.overlap)
         self.inner = DistributedInner(self.part, mesh, self.dist, self.group)
         return mesh
 

@@ -90,7 +90,7 @@ class ConvectionDiffusionSolver:
                  T_W: float = None, T_E: float = None, T_S: float = None, T_N: float = None,
                  mtol=1e-7, iprint: list = [], krylov: str = "device", max_basis: int = 2000,  # noqa: B006
                  partition=None, recycle_bytes: float = 0.0, precond: str = "condensed",
-                 partition_update: str = "distributed"):
+                 partition_update: str = "distributed", partition_adjoint: bool = False):
         """partition: a sem_amd.parallel.Partition -- the solver then holds one element-column strip
         per rank, every apply ends with the interface exchange (overlapped with the interior) and
         the Krylov inner products are all-reduced; the reference methods still take and return
@@ -101,7 +101,11 @@ class ConvectionDiffusionSolver:
         Jacobian (strip_solve.StripLineSolver: each rank factors its own columns, the ranks share a
         reduced system over the strip-boundary lines); "central": the Sys velocity field and the
         right-hand side are gathered, rank 0's whole-mesh counterpart (_central_solver) solves with
-        the condensed direct preconditioner, the update is broadcast."""
+        the condensed direct preconditioner, the update is broadcast.
+        partition_adjoint: opt-in to reverse mode on a partitioned solver -- _get_dresiduals_T and
+        _get_update_T then run over the strips (parallel.StripApplyT: each rank's transposed strip apply
+        + the interface exchange); the adjoint solve is the UNPRECONDITIONED distributed GMRES (there is no
+        transposed strip condensation).  Off by default: a partitioned solver refuses both methods."""
         if krylov not in ("device", "scipy"):
             raise ValueError("krylov must be 'device' or 'scipy'")
         if partition is not None and krylov != "device":
@@ -113,6 +117,7 @@ class ConvectionDiffusionSolver:
         if partition_update not in ("distributed", "central"):
             raise ValueError("partition_update must be 'distributed' or 'central'")
         self._partition_update = partition_update
+        self._partition_adjoint = bool(partition_adjoint)
         self._args = dict(L_x=L_x, L_y=L_y, Pe=Pe, P=P, N_ex=N_ex, N_ey=N_ey, T_W=T_W, T_E=T_E, T_S=T_S, T_N=T_N,
                           mtol=mtol, iprint=iprint, max_basis=max_basis, precond=precond)
         self._twin, self._sys_uv, self._twin_stale = None, None, True
@@ -214,10 +219,11 @@ class ConvectionDiffusionSolver:
         y = self._apply(self._dev(dT), dir_mode=_lib.DIR_IDENTITY, **self._sys_kw(), **self._dir.kw(), **kw)
         return self._out(y, dT)
 
-    def _whole_mesh_only(self, what):
-        if self._part is not None:
-            raise ValueError(f"ConvectionDiffusion: {what} is implemented for whole-mesh solvers only "
-                             "(no transposed strip apply)")
+    def _whole_mesh_only(self, what, adjoint=False):
+        """Refuse `what` on a partitioned solver; adjoint=True: unless partition_adjoint opted in."""
+        if self._part is not None and not (adjoint and getattr(self, "_partition_adjoint", False)):
+            raise ValueError(f"ConvectionDiffusion: {what} is implemented for whole-mesh solvers only" +
+                             (" unless the partitioned solver was built with partition_adjoint=True" if adjoint else ""))
 
     def _operator(self, x, c_mass=0.0, c_stiff=0.0, cu=None, cv=None, free=False):
         """(c_mass M + c_stiff K + diag(cu) G_x + diag(cv) G_y) x on this solver's mesh in one fused launch, no
@@ -237,15 +243,20 @@ class ConvectionDiffusionSolver:
         return self._out(y, x)
 
     def _apply_T(self, w, y=None, **kw):
-        """A_D^T w: one fused transposed launch of Sys with identity Dirichlet rows."""
-        return self._mesh.apply_transpose(w, y, dir_mode=_lib.DIR_IDENTITY, **self._sys_kw(), **self._dir.kw(), **kw)
+        """A_D^T w: one fused transposed launch of Sys with identity Dirichlet rows; on a partitioned solver
+        the transposed strip apply with the interface exchange (partition.step_T; w agrees on shared lines)."""
+        launch = self._mesh.apply_transpose if self._part is None else self._part.step_T
+        return launch(w, y, dir_mode=_lib.DIR_IDENTITY, **self._sys_kw(), **self._dir.kw(), **kw)
 
     def _get_dresiduals_T(self, dres_bar):
         """Transpose of _get_dresiduals(dT, du, dv): (dT_bar, du_bar, dv_bar) with
         dT_bar = A_D^T dres_bar, du_bar = (Pe G_x T) (1 - m) dres_bar, dv_bar = (Pe G_y T) (1 - m) dres_bar
         (m = the Dirichlet mask), so that <_get_dresiduals(dT, du, dv), w> = <dT, dT_bar> + <du, du_bar> +
-        <dv, dv_bar>.  Needs _get_residuals and _calc_jacobians, like the forward method."""
-        self._whole_mesh_only("_get_dresiduals_T")
+        <dv, dv_bar>.  Needs _get_residuals and _calc_jacobians, like the forward method.  On a partitioned
+        solver (partition_adjoint=True) dT_bar is assembled by the interface exchange; the two pointwise
+        products are local to every node and need none.  NumPy in, gathered NumPy out; local tensors in (equal
+        on shared lines), local tensors out."""
+        self._whole_mesh_only("_get_dresiduals_T", adjoint=True)
         if self._Sys is None or self._Jac_T_u is None:
             raise RuntimeError("ConvectionDiffusion: _get_residuals and _calc_jacobians must run before "
                                "_get_dresiduals_T")
@@ -263,8 +274,12 @@ class ConvectionDiffusionSolver:
         (the default) it is right-preconditioned, as the forward solve is, by the condensed direct factor
         applied transposed (VelocityJacobianSolver.solve1_T: the same factor, no second one; restart at most
         100; on the GPU the transposed solve is captured in a graph on its first use); the stopping test stays
-        on the true residual.  precond=None: the unpreconditioned solve."""
-        self._whole_mesh_only("_get_update_T")
+        on the true residual.  precond=None: the unpreconditioned solve.
+        On a partitioned solver (partition_adjoint=True) every iteration is a transposed strip apply plus the
+        interface exchange, the inner products are all-reduced (partition.inner), the restart comes from the
+        global N and is the same on every rank, and the solve is NOT preconditioned whatever `precond` says:
+        there is no transposed strip condensation (StripLineSolver has no solve1_T)."""
+        self._whole_mesh_only("_get_update_T", adjoint=True)
         if self._Sys is None:
             raise RuntimeError("ConvectionDiffusion: _get_residuals must run before _get_update_T")
         b = self._dev(dT_bar)
@@ -278,7 +293,9 @@ class ConvectionDiffusionSolver:
 
         restart = max(1, min(int(self.N * 0.3), self._max_basis))
         kw = {}
-        if self._precond == "condensed":
+        if self._part is not None:
+            kw = dict(inner=self._part.inner)
+        elif self._precond == "condensed":
             vs = self._jacobian_solver()
             if vs.device.type == "cuda" and vs._graph_T is None:
                 vs.capture_T()
