@@ -703,6 +703,35 @@ int sem_ns_apply(sem_handle* h, const sem_ns_desc* d, const double* u, const dou
 int sem_ns_apply_transpose(sem_handle* h, const sem_ns_desc* d, const double* zu, const double* zv, const double* zc,
                            double* yu, double* yv, double* yp, double* yT, void* stream);
 
+/* The transposed Navier-Stokes apply of ANY handle (entry point added at ABI 15): (yu, yv, yp) = A_s^T (zu, zv, zc) and
+ * yT in one launch, where A_s is the 3 n_local x 3 n_local matrix sem_ns_apply applies on this handle with T, dval_u,
+ * dval_v NULL and pin_val 0.  sem_ns_apply_transpose stays the whole-mesh form with its refusal; on a whole-mesh
+ * handle the two launch the same kernel with the same arguments (bitwise-equal results).
+ * Strip handles (ex_begin > 0 or ex_end < nex).  The forward partitioned apply is A = sum_s R_s^T A_s R_s (R_s: the
+ * restriction to strip s's lines), hence A^T z = sum_s R_s^T A_s^T R_s z: each strip applies A_s^T to its slice of z and
+ * the interface exchange of the forward step (sem_interface_pack / unpack around a sum, or the neighbour exchange)
+ * assembles the shared lines.  z must hold EQUAL values on a shared line in both strips that hold it.  A_s is
+ *   - in x, the operator of a mesh of the strip's own ncols = ex_end - ex_begin element columns: the assembled
+ *     weights and the K and G rows stop at the strip's first and last line, so BOTH interface lines carry the partial
+ *     sums of the strip's own elements, and the boundary term of the transposed gradient, G_x^T = -G_x + B, sits on
+ *     the strip's own first and last line (the interface parts cancel in the exchange); y is unchanged;
+ *   - on the right interface line (ex_end < nex), which the strip on the right owns: with all-zero Dirichlet velocity
+ *     rows and pinned row and without the j** terms.  This strip therefore forms z' = (1 - m) z, w = c_div (1 - m_c) zc
+ *     and k = m_b zc there like everywhere (the divergence rows, the (K p) rows and the c_T M T term are partial sums
+ *     on that line too; a pin that rc keeps there gives w = k = 0) but adds none of m zu, m zv, juu / juv / jvu / jvv
+ *     or e_pin zc[pin] on that line; the right-hand owner, for which the line is its (owned) first line, adds them.
+ *   yT = c_T M_s z'_v with the strip's own weights: a partial sum on both interface lines.
+ * dir_sides: W and E act only where the strip touches the mesh boundary (ex_begin == 0, ex_end == nex).  dir_mask,
+ * every operand and every output hold the handle's n_local nodes, indexed from its first line (line views: its own
+ * lines); `pin` stays a GLOBAL node index, and a pin outside the strip is no pin.
+ * uv_pitch, NULL inputs and outputs, the aliasing rules, the four specialised forms, determinism (no atomics, nothing
+ * allocated, graph-capturable) and the statuses are those of sem_ns_apply_transpose, except that no handle is refused
+ * for being a strip and that the 32-bit limit reads on the handle's own lines (n_local or
+ * (line_end - line_begin) uv_pitch + NY above 2^31 - 1).  sem_ns_desc has no position range: the forward
+ * Navier-Stokes step does not overlap its exchange.  y* are not written when a status is returned. */
+int sem_ns_apply_transpose_part(sem_handle* h, const sem_ns_desc* d, const double* zu, const double* zv,
+                                const double* zc, double* yu, double* yv, double* yp, double* yT, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,7 +38,20 @@
 // LDS: one pass per direction over the node's element row(s), each staged value and table entry read once and feeding
 // all the sums that use it, then the pointwise terms and the stores.  The form flags fix at compile time which operands
 // are staged and which sums are formed for the forms the solvers launch (transposed gradient: zc -> yu, yv;
-// transposed divergence: zu, zv, zc -> yp; velocity rows: zu, zv -> yu, yv; everything).  Whole-mesh handles only.
+// transposed divergence: zu, zv, zc -> yp; velocity rows: zu, zv -> yu, yv; everything).
+//
+// Strips (sem_ns_apply_transpose_part).  The matrix A_s that sem_ns_apply applies on a strip handle is the operator of
+// the sub-mesh of the strip's own element columns with the owner rule on its right interface line, so the kernel runs
+// on strip-local geometry: NX, nex, every gx, the mask index and the pin count from the strip's first line (a pin
+// outside the strip is no pin), the 1-D x weights, the K and G rows and the boundary term b_x of G_x^T stop at / sit on
+// the STRIP's first and last line (the interface parts cancel in the exchange), and the W / E side bits reach the
+// kernel only where the strip touches the mesh boundary.  On a right interface line the forward pinned row and
+// Dirichlet velocity rows are all zero and the j** terms are the right-hand owner's: z', w, k are staged there as
+// everywhere (a kept pin gives w = k = 0 on any line), and m zu, m zv, the j** terms and e_pin zc[pin] are not added.
+// That line is the one line of the ghost position tx = nex, so the gate is workgroup-uniform (tx < nex), and it
+// exists only in the PART = true instantiations, which a handle with a right interface line launches.  A handle
+// that owns its last line runs PART = false: the kernel arguments and the instruction stream of the whole-mesh
+// kernel as it was before strips (profiles/ns_strip_adjoint/ab_summary.txt: why the axis exists).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -59,8 +72,8 @@ struct NsTArgs {
   double fT, c_div;             // c_T dx dy/4
   int pitch;                    // node (gx, gy) of zu, zv, yu, yv at gx * pitch + gy
   int pin;                      // pinned node, -1: none
-  int NY, NX, nex, ney, pin_first;
-  unsigned sides;
+  int NY, NX, nex, ney, pin_first;  // NX, nex: the handle's own lines / element columns
+  unsigned sides;                    // W, E: only where the handle touches the mesh boundary
 };
 
 enum : int { NT_ZUV = 1, NT_ZC = 2, NT_YUV = 4, NT_YP = 8, NT_ALL = 15 };
@@ -141,7 +154,8 @@ __device__ __forceinline__ bool nst_pin(const NsTArgs& a, int q, bool dir) {
   return q == a.pin && (!a.pin_first || !dir);
 }
 
-template <int P, int F>
+// PART = true: a strip with a right interface line (ex_end < nex), whose pointwise terms are its right-hand owner's.
+template <int P, int F, bool PART>
 __global__ __launch_bounds__((NsTTile<P>::THREADS)) void ns_apply_transpose_tile(const NsTArgs a, int tiles_y, int ntiles, int per_xcd) {
   using T = NsTTile<P>;
   using M = NsTForm<F>;
@@ -210,6 +224,7 @@ __global__ __launch_bounds__((NsTTile<P>::THREADS)) void ns_apply_transpose_tile
   const bool want_uv = M::YUV && (a.yu || a.yv);  // yT is pointwise: it needs none of the rows
   const bool want_T = M::YUV && a.yT;
   const bool want_p = M::YP && a.yp;
+  const bool own = !PART || tx < a.nex;  // false in the ghost position (the closing line) of a PART launch only
   static_assert(BX * BY <= T::THREADS, "one owned node per thread");
   for (int k = threadIdx.x; k < BX * BY; k += T::THREADS) {  // one trip
     const int ox = k / BY, oy = k - ox * BY;
@@ -296,24 +311,24 @@ __global__ __launch_bounds__((NsTTile<P>::THREADS)) void ns_apply_transpose_tile
         if (a.yu) {
           double z = su;
           if constexpr (M::SYS) {
-            if (a.juu) z = fma(a.juu[q], zu0, z);
-            if (a.jvu) z = fma(a.jvu[q], zv0, z);
+            if (own && a.juu) z = fma(a.juu[q], zu0, z);
+            if (own && a.jvu) z = fma(a.jvu[q], zv0, z);
           }
           if constexpr (M::GW) z = fma(a.hy * my, bx * sW[sidx] - gwx, z);
           if constexpr (M::ZUV) {
-            if (dir && a.zu) z += a.zu[qv];  // m zu
+            if (own && dir && a.zu) z += a.zu[qv];  // m zu
           }
           a.yu[qv] = z;
         }
         if (a.yv) {
           double z = sv;
           if constexpr (M::SYS) {
-            if (a.juv) z = fma(a.juv[q], zu0, z);
-            if (a.jvv) z = fma(a.jvv[q], zv0, z);
+            if (own && a.juv) z = fma(a.juv[q], zu0, z);
+            if (own && a.jvv) z = fma(a.jvv[q], zv0, z);
           }
           if constexpr (M::GW) z = fma(a.hx * mx, by * sW[sidx] - gwy, z);
           if constexpr (M::ZUV) {
-            if (dir && a.zv) z += a.zv[qv];  // m zv
+            if (own && dir && a.zv) z += a.zv[qv];  // m zv
           }
           a.yv[qv] = z;
         }
@@ -329,7 +344,7 @@ __global__ __launch_bounds__((NsTTile<P>::THREADS)) void ns_apply_transpose_tile
           z = fma(a.sy * mx, ky, z);
         }
         if constexpr (M::ZC) {
-          if (a.zc && nst_pin(a, q, dir)) z += a.zc[q];  // e_pin zc[pin]
+          if (own && a.zc && nst_pin(a, q, dir)) z += a.zc[q];  // e_pin zc[pin]
         }
         a.yp[q] = z;
       }
@@ -338,55 +353,58 @@ __global__ __launch_bounds__((NsTTile<P>::THREADS)) void ns_apply_transpose_tile
 }
 
 template <int P, int F>
-static int launch_ns_transpose(const NsTArgs& a, hipStream_t s) {
+static int launch_ns_transpose(const NsTArgs& a, bool open_right, hipStream_t s) {
   using T = NsTTile<P>;
-  const int tiles_x = a.nex + 1;  // positions 0..nex (nex: the closing line)
+  const int tiles_x = a.nex + 1;  // positions 0..nex of the handle's own columns (nex: the closing line)
   const int tiles_y = (a.ney + T::TYE) / T::TYE;
   const long long ntiles = static_cast<long long>(tiles_x) * tiles_y;
   const long long per_xcd = (ntiles + 7) / 8;
   if (8 * per_xcd > 0x7fffffffLL) return set_error(SEM_EUNSUPPORTED, "mesh too large for one launch");
-  hipLaunchKernelGGL((ns_apply_transpose_tile<P, F>), dim3(static_cast<unsigned>(8 * per_xcd)), dim3(T::THREADS), 0, s, a,
-                     tiles_y, static_cast<int>(ntiles), static_cast<int>(per_xcd));
+  const dim3 grid(static_cast<unsigned>(8 * per_xcd)), block(T::THREADS);
+  if (open_right)
+    hipLaunchKernelGGL((ns_apply_transpose_tile<P, F, true>), grid, block, 0, s, a, tiles_y, static_cast<int>(ntiles),
+                       static_cast<int>(per_xcd));
+  else
+    hipLaunchKernelGGL((ns_apply_transpose_tile<P, F, false>), grid, block, 0, s, a, tiles_y, static_cast<int>(ntiles),
+                       static_cast<int>(per_xcd));
   return SEM_OK;
 }
 
-}  // namespace sem
-
-extern "C" {
-
-int sem_ns_apply_transpose(sem_handle* h, const sem_ns_desc* d, const double* zu, const double* zv, const double* zc,
-                           double* yu, double* yv, double* yp, double* yT, void* stream) {
-  if (!h || !d) return sem::set_error(SEM_EINVAL, "null argument");
-  if (d->uv_pitch != 0 && d->uv_pitch < h->NY) return sem::set_error(SEM_EINVAL, "uv_pitch below the line length");
-  if (d->pin < -1 || d->pin >= h->NX * h->NY) return sem::set_error(SEM_EINVAL, "pinned node out of range");
+// The two entry points: `part` lifts the strip refusal; everything else is one contract.
+static int ns_transpose(const char* name, bool part, sem_handle* h, const sem_ns_desc* d, const double* zu,
+                        const double* zv, const double* zc, double* yu, double* yv, double* yp, double* yT, void* stream) {
+  if (!h || !d) return set_error(SEM_EINVAL, "null argument");
+  if (d->uv_pitch != 0 && d->uv_pitch < h->NY) return set_error(SEM_EINVAL, "uv_pitch below the line length");
+  if (d->pin < -1 || d->pin >= h->NX * h->NY) return set_error(SEM_EINVAL, "pinned node out of range");
   if (d->T || d->dval_u || d->dval_v || d->pin_val != 0.0)
-    return sem::set_error(SEM_EINVAL, "the transposed apply is that of the linear part: T, dval_u, dval_v must be NULL "
-                                      "and pin_val 0");
+    return set_error(SEM_EINVAL, "the transposed apply is that of the linear part: T, dval_u, dval_v must be NULL "
+                                 "and pin_val 0");
   const double* const ins[3] = {zu, zv, zc};
   const double* const outs[4] = {yu, yv, yp, yT};
   for (const double* o : outs)
     for (const double* i : ins)
-      if (o && o == i) return sem::set_error(SEM_EINVAL, "an output aliases an input");
+      if (o && o == i) return set_error(SEM_EINVAL, "an output aliases an input");
   if (d->uv_pitch != 0 && d->uv_pitch != h->NY) {
     // cu, cv are plain vectors, zu, zv line views: the same pointer would name different nodes
     if (d->cu && (d->cu == zu || d->cu == zv))
-      return sem::set_error(SEM_EINVAL, "cu aliases zu or zv, but they are line views (uv_pitch != NY)");
+      return set_error(SEM_EINVAL, "cu aliases zu or zv, but they are line views (uv_pitch != NY)");
     if (d->cv && (d->cv == zu || d->cv == zv))
-      return sem::set_error(SEM_EINVAL, "cv aliases zu or zv, but they are line views (uv_pitch != NY)");
+      return set_error(SEM_EINVAL, "cv aliases zu or zv, but they are line views (uv_pitch != NY)");
   }
   int cur = -1;
   if (hipGetDevice(&cur) != hipSuccess || cur != h->device)
-    return sem::set_error(SEM_EINVAL, "handle belongs to device " + std::to_string(h->device) +
-                                          ", but the current device is " + std::to_string(cur));
-  if (h->ex_begin != 0 || h->ex_end != h->nex)
-    return sem::set_error(SEM_EUNSUPPORTED, "sem_ns_apply_transpose: whole-mesh handles only (no transposed strip apply)");
+    return set_error(SEM_EINVAL, "handle belongs to device " + std::to_string(h->device) +
+                                     ", but the current device is " + std::to_string(cur));
+  if (!part && (h->ex_begin != 0 || h->ex_end != h->nex))
+    return set_error(SEM_EUNSUPPORTED, "sem_ns_apply_transpose: whole-mesh handles only (no transposed strip apply)");
   const int64_t pitch = d->uv_pitch ? d->uv_pitch : h->NY;
+  const int64_t lines = h->line_end - h->line_begin + 1;  // the handle's own lines (NX on a whole mesh)
   // the kernel addresses every vector through 32-bit node offsets
-  if (h->n_local > 0x7fffffffLL || (h->NX - 1) * pitch + h->NY > 0x7fffffffLL)
-    return sem::set_error(SEM_EUNSUPPORTED, "sem_ns_apply_transpose: mesh past the 32-bit node-offset limit "
-                                            "(n_local or (NX - 1) uv_pitch + NY above 2^31 - 1)");
+  if (h->n_local > 0x7fffffffLL || (lines - 1) * pitch + h->NY > 0x7fffffffLL)
+    return set_error(SEM_EUNSUPPORTED, std::string(name) + ": mesh past the 32-bit node-offset limit "
+                                                           "(n_local or (NX - 1) uv_pitch + NY above 2^31 - 1)");
   if (!yu && !yv && !yp && !yT) return SEM_OK;
-  sem::NsTArgs a{};
+  NsTArgs a{};
   a.zu = zu;
   a.zv = zv;
   a.zc = zc;
@@ -401,7 +419,8 @@ int sem_ns_apply_transpose(sem_handle* h, const sem_ns_desc* d, const double* zu
   a.jvu = d->jvu;
   a.jvv = d->jvv;
   a.mask = d->dir_mask;
-  a.sides = d->dir_sides;
+  // W and E are mesh sides: a strip's first / last line is one only where the strip touches the boundary
+  a.sides = d->dir_sides & ~((h->ex_begin != 0 ? SEM_SIDE_W : 0u) | (h->ex_end != h->nex ? SEM_SIDE_E : 0u));
   const double dx = h->dx, dy = h->dy;
   a.fKx = d->c_stiff * (dy / dx);
   a.fKy = d->c_stiff * (dx / dy);
@@ -415,27 +434,43 @@ int sem_ns_apply_transpose(sem_handle* h, const sem_ns_desc* d, const double* zu
   a.fT = d->c_T * ((dx / 2.0) * (dy / 2.0));
   a.c_div = d->c_div;
   a.pitch = static_cast<int>(pitch);
-  a.pin = static_cast<int>(d->pin);
+  // the pin is a global node; the kernel counts nodes from the handle's first line (outside the strip: no pin)
+  const int64_t pin = d->pin < 0 ? -1 : d->pin - h->line_begin * h->NY;
+  a.pin = pin >= 0 && pin < h->n_local ? static_cast<int>(pin) : -1;
   a.pin_first = d->pin_first;
   a.NY = static_cast<int>(h->NY);
-  a.NX = static_cast<int>(h->NX);
-  a.nex = h->nex;
+  a.NX = static_cast<int>(lines);
+  a.nex = h->ex_end - h->ex_begin;
   a.ney = h->ney;
+  const bool open_right = h->ex_end != h->nex;  // a right interface line: its right-hand owner's pointwise terms
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // the forms the solvers launch run specialised kernels: the transposed divergence (yp alone out), the transposed
   // gradient (zc alone in; yu, yv out) and the velocity rows (zu, zv in; yu, yv out); anything else the full form
   const bool uv_in = zu || zv, uv_out_only = !yp && !yT;
-  constexpr int kGradT = sem::NT_ZC | sem::NT_YUV, kDivT = sem::NT_ZUV | sem::NT_ZC | sem::NT_YP,
-                kVelT = sem::NT_ZUV | sem::NT_YUV;
-  const int st = sem::dispatch_order(h->P, [&](auto PC) {
+  constexpr int kGradT = NT_ZC | NT_YUV, kDivT = NT_ZUV | NT_ZC | NT_YP, kVelT = NT_ZUV | NT_YUV;
+  const int st = dispatch_order(h->P, [&](auto PC) {
     constexpr int P = decltype(PC)::value;
-    if (yp && !yu && !yv && !yT) return sem::launch_ns_transpose<P, kDivT>(a, s);
-    if (uv_out_only && !uv_in) return sem::launch_ns_transpose<P, kGradT>(a, s);
-    if (uv_out_only && !zc) return sem::launch_ns_transpose<P, kVelT>(a, s);
-    return sem::launch_ns_transpose<P, sem::NT_ALL>(a, s);
+    if (yp && !yu && !yv && !yT) return launch_ns_transpose<P, kDivT>(a, open_right, s);
+    if (uv_out_only && !uv_in) return launch_ns_transpose<P, kGradT>(a, open_right, s);
+    if (uv_out_only && !zc) return launch_ns_transpose<P, kVelT>(a, open_right, s);
+    return launch_ns_transpose<P, NT_ALL>(a, open_right, s);
   });
   if (st) return st;
-  return sem::hip_check(hipGetLastError(), "ns apply (transpose) launch");
+  return hip_check(hipGetLastError(), "ns apply (transpose) launch");
+}
+
+}  // namespace sem
+
+extern "C" {
+
+int sem_ns_apply_transpose(sem_handle* h, const sem_ns_desc* d, const double* zu, const double* zv, const double* zc,
+                           double* yu, double* yv, double* yp, double* yT, void* stream) {
+  return sem::ns_transpose("sem_ns_apply_transpose", false, h, d, zu, zv, zc, yu, yv, yp, yT, stream);
+}
+
+int sem_ns_apply_transpose_part(sem_handle* h, const sem_ns_desc* d, const double* zu, const double* zv, const double* zc,
+                                double* yu, double* yv, double* yp, double* yT, void* stream) {
+  return sem::ns_transpose("sem_ns_apply_transpose_part", true, h, d, zu, zv, zc, yu, yv, yp, yT, stream);
 }
 
 }  // extern "C"

@@ -255,15 +255,17 @@ class Mesh:
                                                   self.stream_ptr(stream)))
         return blocks
 
-    def _line_view(self, t, name):
-        """u, v, ru, rv of sem_ns_apply: a plain vector, or an (NX, NY) view with row stride >= NY."""
+    def _line_view(self, t, name, lines=None):
+        """u, v, ru, rv of sem_ns_apply: a plain vector, or an (NX, NY) view with row stride >= NY (lines: the
+        line count of the view when it is not NX)."""
+        NX = self.NX if lines is None else lines
         if t is None:
             return None, 0
         if t.dim() == 1:
             return self._vec(t, name), 0
         if (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.float64
-                or tuple(t.shape) != (self.NX, self.NY) or t.stride(1) != 1 or t.stride(0) < self.NY):
-            raise ValueError(f"{name} must be a float64 ({self.NX}, {self.NY}) line view on {self.device}")
+                or tuple(t.shape) != (NX, self.NY) or t.stride(1) != 1 or t.stride(0) < self.NY):
+            raise ValueError(f"{name} must be a float64 ({NX}, {self.NY}) line view on {self.device}")
         return t, t.stride(0)
 
     def ns_apply(self, u=None, v=None, p=None, ru=None, rv=None, rc=None, *, c_mass=0.0, c_stiff=0.0, c_gradx=0.0,
@@ -305,10 +307,34 @@ class Mesh:
         yu, yv are plain vectors or (NX, NY) line views sharing one row stride; a None input is zeros, a None output
         is not computed.  Whole-mesh handles only.  T, dval_u, dval_v and pin_val are the descriptor fields the
         transpose of the linear part does not take: the library refuses them as the header documents."""
+        return self._ns_transpose(self._lib.sem_ns_apply_transpose, zu, zv, zc, yu, yv, yp, yT, c_mass, c_stiff,
+                                  c_gradx, c_grady, cu, cv, juu, juv, jvu, jvv, c_T, T, c_div, dval_u, dval_v, dir_mask,
+                                  dir_sides, pin, pin_val, pin_first, stream)
+
+    def ns_apply_transpose_part(self, zu=None, zv=None, zc=None, yu=None, yv=None, yp=None, yT=None, *, c_mass=0.0,
+                                c_stiff=0.0, c_gradx=0.0, c_grady=0.0, cu=None, cv=None, juu=None, juv=None, jvu=None,
+                                jvv=None, c_T=0.0, T=None, c_div=1.0, dval_u=None, dval_v=None, dir_mask=None,
+                                dir_sides=0, pin=-1, pin_val=0.0, pin_first=False, stream=None):
+        """ns_apply_transpose for this handle's own matrix (include/sem_ops.h, sem_ns_apply_transpose_part):
+        (yu, yv, yp) = A_s^T (zu, zv, zc) and yT for the A_s that `ns_apply` applies here -- on a strip the partial
+        sums of its own elements on both interface lines, the pointwise terms, Dirichlet entries and the pinned row
+        of the right interface line left to its right-hand owner -- so that summing the strips' results over the
+        shared lines (the forward exchange) gives the whole mesh's A^T z; z must agree on shared lines.  Line views
+        hold the handle's own lines; `pin` stays a global node index.  On a whole-mesh handle: bitwise
+        ns_apply_transpose."""
+        return self._ns_transpose(self._lib.sem_ns_apply_transpose_part, zu, zv, zc, yu, yv, yp, yT, c_mass, c_stiff,
+                                  c_gradx, c_grady, cu, cv, juu, juv, jvu, jvv, c_T, T, c_div, dval_u, dval_v, dir_mask,
+                                  dir_sides, pin, pin_val, pin_first, stream,
+                                  lines=int(self.line_end - self.line_begin + 1))
+
+    def _ns_transpose(self, entry, zu, zv, zc, yu, yv, yp, yT, c_mass, c_stiff, c_gradx, c_grady, cu, cv, juu, juv, jvu,
+                      jvv, c_T, T, c_div, dval_u, dval_v, dir_mask, dir_sides, pin, pin_val, pin_first, stream,
+                      lines=None):
+        """The checks and the descriptor of the two transposed Navier-Stokes entry points."""
         pitch = set()
         views = []
         for nm, t in (("zu", zu), ("zv", zv), ("yu", yu), ("yv", yv)):
-            t, s = self._line_view(t, nm)
+            t, s = self._line_view(t, nm, lines)
             views.append(t)
             if t is not None:
                 pitch.add(s)
@@ -323,9 +349,8 @@ class Mesh:
                            _ptr(juu), _ptr(juv), _ptr(jvu), _ptr(jvv), float(c_T), _ptr(T), float(c_div),
                            _ptr(dval_u), _ptr(dval_v), _ptr(dir_mask), int(dir_sides), int(bool(pin_first)), int(pin),
                            float(pin_val), pitch.pop() if pitch else 0)
-        _lib.check(self._lib.sem_ns_apply_transpose(self._h, C.byref(d), *(_ptr(t) for t in views[:2]), _ptr(zc),
-                                                    *(_ptr(t) for t in views[2:]), _ptr(yp), _ptr(yT),
-                                                    self.stream_ptr(stream)))
+        _lib.check(entry(self._h, C.byref(d), *(_ptr(t) for t in views[:2]), _ptr(zc), *(_ptr(t) for t in views[2:]),
+                         _ptr(yp), _ptr(yT), self.stream_ptr(stream)))
         return views[2], views[3], yp, yT
 
     # ------------------------------------------------------------------ host-side 1-D tables

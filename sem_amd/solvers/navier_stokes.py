@@ -55,7 +55,7 @@ class NavierStokesSolver:
                  mtol=1e-7, mtol_newton=1e-5, iprint: list = ['NEWTON_suc', 'NEWTON_iter'],  # noqa: B006
                  max_basis: int = 3000, velocity_interior: str = "auto", velocity_graph: bool = True,
                  recycle_bytes: float = 0.0, velocity_sweep: str = "auto", schur_precond: str = "mass",
-                 partition=None, partition_update: str = "distributed"):
+                 partition=None, partition_update: str = "distributed", partition_adjoint: bool = False):
         """partition: a sem_amd.parallel.Partition -- the solver then holds one element-column strip per
         rank: _get_residuals / _calc_jacobians / _get_dresiduals run the fused strip launch and sum the
         interface lines of all three outputs with one collective.  partition_update: "distributed"
@@ -65,6 +65,13 @@ class NavierStokesSolver:
         solve runs over the strips (inner products all-reduced); "central" -- rank 0's whole-mesh
         counterpart (_central_solver) solves and the update is broadcast.  The reference methods take
         and return global NumPy vectors (local strips when given device tensors).
+        partition_adjoint: opt-in to reverse mode on a partitioned solver.  _get_dresiduals_T then runs on the
+        strips (one Mesh.ns_apply_transpose_part launch per rank, one collective for the interface lines).
+        _get_update_T is the FUNCTIONAL path, not the scalable one: whatever partition_update says it runs
+        centrally -- the linearisation and the right-hand sides are gathered, rank 0's whole-mesh counterpart
+        solves, the result is broadcast; a distributed adjoint Schur solve waits for the transposed strip solvers.
+        velocity_solve_T and _velocity_apply_lines_T stay whole-mesh only.  Off by default: a partitioned solver
+        refuses every reverse-mode method.
         recycle_bytes: device memory for a recycled Krylov subspace of the Schur-complement solves
         (sem_amd.krylov.Recycle, GCRO; 0 = off, the default): consecutive _get_update calls with one
         linearisation -- the Boussinesq coupler's block-Jacobi preconditioner -- then start from the
@@ -97,6 +104,7 @@ class NavierStokesSolver:
         if partition is not None and schur_precond != "mass" and partition_update == "distributed":
             raise ValueError("the distributed update uses the mass-diagonal Schur preconditioner")
         self._partition_update = partition_update
+        self._partition_adjoint = bool(partition_adjoint)
         self._schur_precond, self._Ap = schur_precond, None
         self._iprint = iprint
         self._recycle_bytes, self._schur_recycle = recycle_bytes, None
@@ -474,10 +482,12 @@ class NavierStokesSolver:
         self._part.assemble(ru, rv)
         return torch.stack((ru.view(-1, NY), rv.view(-1, NY)), dim=1).reshape(-1, 2 * NY)
 
-    def _whole_mesh_only(self, what):
-        if self._part is not None:
-            raise ValueError(f"NavierStokes: {what} is implemented for whole-mesh solvers only "
-                             "(no transposed strip apply, no transposed strip solve)")
+    def _whole_mesh_only(self, what, adjoint=False):
+        """Refuse `what` on a partitioned solver; adjoint=True: unless partition_adjoint opted in."""
+        if self._part is not None and not (adjoint and self._partition_adjoint):
+            raise ValueError(f"NavierStokes: {what} is implemented for whole-mesh solvers only " +
+                             ("unless the partitioned solver was built with partition_adjoint=True" if adjoint else
+                              "(no transposed strip solve)"))
 
     def _velocity_apply_lines_T(self, X):
         """J_D^T X for the velocity Jacobian of this linearisation on (NX, 2 NY) line arrays (the transpose of
@@ -637,22 +647,29 @@ class NavierStokesSolver:
             y = self._free * y
         return self._out(y, x)
 
-    # ------------------------------------------------------------------ reverse mode (whole mesh)
+    # ------------------------------------------------------------------ reverse mode
     def _get_dresiduals_T(self, ru_bar, rv_bar, rc_bar, want_T=False):
         """Transpose of _get_dresiduals(du, dv, dp, dT): (du_bar, dv_bar, dp_bar) = A^T (ru_bar, rv_bar, rc_bar) for
         the operator A of _get_dresiduals at dT = 0, and with want_T also dT_bar = -(Gr/Re) M (1 - m) rv_bar, so that
         <_get_dresiduals(d), w> = <d, _get_dresiduals_T(w)> -- one fused launch (sem_ns_apply_transpose).  NumPy in,
-        NumPy out; device tensors in, device tensors out.  Needs _calc_jacobians, like the forward method."""
-        self._whole_mesh_only("_get_dresiduals_T")
+        NumPy out; device tensors in, device tensors out.  Needs _calc_jacobians, like the forward method.
+        On a partitioned solver (partition_adjoint=True): each rank's transposed strip launch
+        (sem_ns_apply_transpose_part) and one collective that sums the interface lines of all outputs; with shared
+        lines counted once the inner-product identity holds.  Global NumPy in, gathered NumPy out; local tensors in
+        (equal on shared lines), local tensors out."""
+        self._whole_mesh_only("_get_dresiduals_T", adjoint=True)
         if self._jac_kw is None:
             raise RuntimeError("NavierStokes: _get_residuals and _calc_jacobians must run before _get_dresiduals_T")
         m = self._mesh
         zu, zv, zc = self._dev(ru_bar), self._dev(rv_bar), self._dev(rc_bar)
         yu, yv, yp = (torch.empty_like(zu) for _ in range(3))
         yT = torch.empty_like(zu) if want_T else None
-        m.ns_apply_transpose(zu, zv, zc, yu, yv, yp, yT, **self._jac_kw, c_T=-self._Gr_over_Re if want_T else 0.0,
-                             **self._ns_kw(pin_first=False))
+        launch = m.ns_apply_transpose if self._part is None else m.ns_apply_transpose_part
+        launch(zu, zv, zc, yu, yv, yp, yT, **self._jac_kw, c_T=-self._Gr_over_Re if want_T else 0.0,
+               **self._ns_kw(pin_first=False))
         out = (yu, yv, yp) + ((yT,) if want_T else ())
+        if self._part is not None:
+            self._part.assemble(*out)
         return tuple(self._out(y, ru_bar) for y in out)
 
     def _get_update_T(self, du_bar, dv_bar, dp_bar, dres_c0=None):
@@ -662,8 +679,12 @@ class NavierStokesSolver:
         lam_c = q, with S^T = E^T - B^T J^-T C^T (_SchurComplementT) solved by the device GMRES under the forward
         update's mass-diagonal right preconditioner, stopping rule (||r||_2 <= mtol sqrt(N)) and restart; dres_c0 is
         the initial guess of q.  No recycling.  Whole-mesh solvers with the nested-dissection factor and
-        schur_precond='mass' only: PCD's A_p^-T would need a transposed line condensation, which does not exist."""
-        self._whole_mesh_only("_get_update_T")
+        schur_precond='mass' only: PCD's A_p^-T would need a transposed line condensation, which does not exist.
+        On a partitioned solver (partition_adjoint=True) the solve runs centrally (_get_update_T_partitioned): the
+        functional path, not the scalable one."""
+        self._whole_mesh_only("_get_update_T", adjoint=True)
+        if self._part is not None:
+            return self._get_update_T_partitioned(du_bar, dv_bar, dp_bar, dres_c0)
         if self._schur_precond == "pcd":
             raise ValueError("NavierStokes: _get_update_T needs schur_precond='mass': the PCD preconditioner's A_p^-T "
                              "would need a transposed line condensation")
@@ -707,6 +728,52 @@ class NavierStokesSolver:
         m.ns_apply_transpose(None, None, q, gu, gv, c_div=-1.0, **kw)    # -C^T q
         lu, lv = vs.solve_T(bu + gu, bv + gv)
         return self._out(lu, du_bar), self._out(lv, du_bar), self._out(q, du_bar)
+
+    def _get_update_T_partitioned(self, du_bar, dv_bar, dp_bar, dres_c0):
+        """_get_update_T of a strip-partitioned solver, run centrally whatever partition_update says (the mirror of
+        _get_update_partitioned): the linearisation and the three right-hand sides are gathered, rank 0's whole-mesh
+        counterpart (the same cached twin) takes the linearisation through _get_residuals / _calc_jacobians when it
+        is stale and runs _get_update_T, and the result is broadcast; a failure on rank 0 travels as a NaN status so
+        that every rank raises.  This is the functional path, not the scalable one: every call moves whole-mesh
+        vectors through rank 0.  A distributed adjoint Schur solve S^T q = E^T q - B^T J^-T C^T q needs the
+        transposed strip solvers, which do not exist yet."""
+        part = self._part
+        lin = self._lin
+        if lin is None:
+            raise RuntimeError("NavierStokes: _get_residuals and _calc_jacobians must run before _get_update_T")
+        stale = lin.get("stale")
+        if stale:
+            us, vs = (self._global(a) for a in lin["sys"])
+            uj, vj = (self._global(a) for a in lin["jac"])
+            lin["stale"] = False
+        rhs = [self._global(a) for a in (du_bar, dv_bar, dp_bar)]
+        q0 = None if dres_c0 is None else self._global(dres_c0)
+        out = torch.zeros(3 * self.N + 1, dtype=torch.float64)
+        err = None
+        if part.rank == 0:
+            try:
+                if stale:
+                    if self._twin is None:
+                        self._twin = self._central_solver()
+                    z = np.zeros(self.N)
+                    self._twin._get_residuals(us, vs, z, z)
+                    self._twin._calc_jacobians(uj, vj)
+                lam = self._twin._get_update_T(*rhs, dres_c0=q0)
+                out[:3 * self.N] = torch.from_numpy(np.concatenate([np.asarray(a) for a in lam]))
+                out[-1] = float(getattr(self._twin, "schur_matvecs", -1))
+            except (RuntimeError, ValueError) as e:
+                err = e
+                out[-1] = float("nan")
+        out = part.broadcast(out)
+        if err is not None:
+            raise err
+        if torch.isnan(out[-1]):
+            raise RuntimeError("NavierStokes: the adjoint update failed on rank 0 (see its error)")
+        self.schur_matvecs = int(out[-1].item())
+        lam = [out[i * self.N:(i + 1) * self.N].cpu().numpy() for i in range(3)]
+        if isinstance(du_bar, torch.Tensor):
+            return tuple(self._dev(a) for a in lam)
+        return tuple(lam)
 
     def _get_solution(self, T, u0=None, v0=None, p0=None):
         """Newton iteration (NavierStokes_Solver.py:238-270), iterates kept on the device; NumPy in,
