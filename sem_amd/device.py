@@ -24,6 +24,9 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+_NS_T_NAMES = ("zu", "zv", "zc", "yu", "yv", "yp", "yT")    # the operands of the transposed Navier-Stokes entries
+
+
 class Mesh:
     """N_ex x N_ey elements of order P with widths dx, dy, holding element columns
     [ex_begin, ex_end) on one GPU (the whole mesh by default)."""
@@ -79,26 +82,38 @@ class Mesh:
         return C.c_void_p(s.cuda_stream)
 
     # ------------------------------------------------------------------ kernels
+    def _mask(self, dir_mask):
+        """The explicit Dirichlet mask of every entry point: uint8, on the mesh's device, n_local entries."""
+        if dir_mask is not None and (dir_mask.dtype != torch.uint8 or dir_mask.device != self.device
+                                     or dir_mask.numel() != self.n_local):
+            raise ValueError("dir_mask must be a uint8 tensor of n_local entries on the mesh device")
+        return dir_mask
+
+    def _apply_launch(self, entry, x, xname, y, c_mass, c_stiff, c_gradx, c_grady, cu, cv, c_extra, ea, ea_name, eb, ec,
+                      ed, c_acc, dir_mode, dir_mask, dir_val, dir_sides, algo, pos, stream):
+        """The checks, the SemApplyDesc and the launch of sem_apply and its two transposed entry points."""
+        x = self._vec(x, xname)
+        if y is None:
+            y = torch.empty_like(x)
+        self._vec(y, "y")
+        for nm, t in (("cu", cu), ("cv", cv), (ea_name, ea), ("eb", eb), ("ec", ec), ("ed", ed), ("dir_val", dir_val)):
+            self._vec(t, nm)
+        self._mask(dir_mask)
+        d = _lib.SemApplyDesc(float(c_mass), float(c_stiff), float(c_gradx), float(c_grady), _ptr(cu), _ptr(cv),
+                              float(c_extra), _ptr(ea), _ptr(eb), _ptr(ec), _ptr(ed), float(c_acc), int(dir_mode),
+                              _ptr(dir_mask), _ptr(dir_val), int(dir_sides), int(algo),
+                              *((0, 0) if pos is None else (int(pos[0]), int(pos[1]))))
+        _lib.check(entry(self._h, C.byref(d), _ptr(x), _ptr(y), self.stream_ptr(stream)))
+        return y
+
     def apply(self, x, y=None, *, c_mass=0.0, c_stiff=0.0, c_gradx=0.0, c_grady=0.0, cu=None, cv=None, c_extra=0.0,
               ea=None, eb=None, ec=None, ed=None, c_acc=0.0, dir_mode=_lib.DIR_NONE, dir_mask=None, dir_val=None,
               dir_sides=0, algo=_lib.ALGO_AUTO, pos=None, stream=None):
         """Fused operator apply (include/sem_ops.h, sem_apply).  pos = (begin, end): write only the
         output lines of those element positions of the strip (0..ncols, ncols = closing line)."""
-        x = self._vec(x, "x")
-        if y is None:
-            y = torch.empty_like(x)
-        self._vec(y, "y")
-        for nm, t in (("cu", cu), ("cv", cv), ("ea", ea), ("eb", eb), ("ec", ec), ("ed", ed), ("dir_val", dir_val)):
-            self._vec(t, nm)
-        if dir_mask is not None:
-            if dir_mask.dtype != torch.uint8 or dir_mask.device != self.device or dir_mask.numel() != self.n_local:
-                raise ValueError("dir_mask must be a uint8 tensor of n_local entries on the mesh device")
-        d = _lib.SemApplyDesc(float(c_mass), float(c_stiff), float(c_gradx), float(c_grady), _ptr(cu), _ptr(cv),
-                              float(c_extra), _ptr(ea), _ptr(eb), _ptr(ec), _ptr(ed), float(c_acc), int(dir_mode),
-                              _ptr(dir_mask), _ptr(dir_val), int(dir_sides), int(algo),
-                              *((0, 0) if pos is None else (int(pos[0]), int(pos[1]))))
-        _lib.check(self._lib.sem_apply(self._h, C.byref(d), _ptr(x), _ptr(y), self.stream_ptr(stream)))
-        return y
+        return self._apply_launch(self._lib.sem_apply, x, "x", y, c_mass, c_stiff, c_gradx, c_grady, cu, cv, c_extra,
+                                  ea, "ea", eb, ec, ed, c_acc, dir_mode, dir_mask, dir_val, dir_sides, algo, pos,
+                                  stream)
 
     def apply_transpose(self, z, y=None, *, c_mass=0.0, c_stiff=0.0, c_gradx=0.0, c_grady=0.0, cu=None, cv=None,
                         diag=None, c_acc=0.0, dir_mode=_lib.DIR_NONE, dir_mask=None, dir_sides=0, stream=None,
@@ -108,21 +123,9 @@ class Mesh:
         Dirichlet rows.  One launch; whole-mesh handles only.  eb, ec, ed, dir_val, algo and pos are the
         remaining descriptor fields: the transposed apply takes none of them and the library refuses
         them as the header documents (ValueError / RuntimeError)."""
-        z = self._vec(z, "z")
-        if y is None:
-            y = torch.empty_like(z)
-        self._vec(y, "y")
-        for nm, t in (("cu", cu), ("cv", cv), ("diag", diag), ("eb", eb), ("ec", ec), ("ed", ed), ("dir_val", dir_val)):
-            self._vec(t, nm)
-        if dir_mask is not None:
-            if dir_mask.dtype != torch.uint8 or dir_mask.device != self.device or dir_mask.numel() != self.n_local:
-                raise ValueError("dir_mask must be a uint8 tensor of n_local entries on the mesh device")
-        d = _lib.SemApplyDesc(float(c_mass), float(c_stiff), float(c_gradx), float(c_grady), _ptr(cu), _ptr(cv),
-                              1.0 if diag is not None else 0.0, _ptr(diag), _ptr(eb), _ptr(ec), _ptr(ed), float(c_acc),
-                              int(dir_mode), _ptr(dir_mask), _ptr(dir_val), int(dir_sides), int(algo),
-                              *((0, 0) if pos is None else (int(pos[0]), int(pos[1]))))
-        _lib.check(self._lib.sem_apply_transpose(self._h, C.byref(d), _ptr(z), _ptr(y), self.stream_ptr(stream)))
-        return y
+        return self._apply_launch(self._lib.sem_apply_transpose, z, "z", y, c_mass, c_stiff, c_gradx, c_grady, cu, cv,
+                                  1.0 if diag is not None else 0.0, diag, "diag", eb, ec, ed, c_acc, dir_mode, dir_mask,
+                                  dir_val, dir_sides, algo, pos, stream)
 
     def apply_transpose_part(self, z, y=None, *, c_mass=0.0, c_stiff=0.0, c_gradx=0.0, c_grady=0.0, cu=None, cv=None,
                              diag=None, c_acc=0.0, dir_mode=_lib.DIR_NONE, dir_mask=None, dir_sides=0, pos=None,
@@ -134,21 +137,9 @@ class Mesh:
         lines (the forward exchange) gives the whole mesh's A_D^T z; z must agree on shared lines.
         pos = (begin, end): write only the output lines of those element positions (0..ncols, ncols = the
         closing line).  eb, ec, ed, dir_val and algo are refused as by apply_transpose."""
-        z = self._vec(z, "z")
-        if y is None:
-            y = torch.empty_like(z)
-        self._vec(y, "y")
-        for nm, t in (("cu", cu), ("cv", cv), ("diag", diag), ("eb", eb), ("ec", ec), ("ed", ed), ("dir_val", dir_val)):
-            self._vec(t, nm)
-        if dir_mask is not None:
-            if dir_mask.dtype != torch.uint8 or dir_mask.device != self.device or dir_mask.numel() != self.n_local:
-                raise ValueError("dir_mask must be a uint8 tensor of n_local entries on the mesh device")
-        d = _lib.SemApplyDesc(float(c_mass), float(c_stiff), float(c_gradx), float(c_grady), _ptr(cu), _ptr(cv),
-                              1.0 if diag is not None else 0.0, _ptr(diag), _ptr(eb), _ptr(ec), _ptr(ed), float(c_acc),
-                              int(dir_mode), _ptr(dir_mask), _ptr(dir_val), int(dir_sides), int(algo),
-                              *((0, 0) if pos is None else (int(pos[0]), int(pos[1]))))
-        _lib.check(self._lib.sem_apply_transpose_part(self._h, C.byref(d), _ptr(z), _ptr(y), self.stream_ptr(stream)))
-        return y
+        return self._apply_launch(self._lib.sem_apply_transpose_part, z, "z", y, c_mass, c_stiff, c_gradx, c_grady, cu,
+                                  cv, 1.0 if diag is not None else 0.0, diag, "diag", eb, ec, ed, c_acc, dir_mode,
+                                  dir_mask, dir_val, dir_sides, algo, pos, stream)
 
     def transpose_kernel_name(self):
         buf = C.create_string_buffer(128)
@@ -193,6 +184,28 @@ class Mesh:
         _lib.check(self._lib.sem_interface_unpack(self._h, _ptr(buf), b, len(bounds) - 1, _ptr(y),
                                                   self.stream_ptr(stream)))
 
+    def _velocity_desc(self, c_mass, c_stiff, c_gradx, c_grady, cu, cv, juu, juv, jvu, jvv, dir_mask, dir_sides, ncomp,
+                       cols):
+        """The checks and the SemVelocityDesc of the two block writers; returns (descriptor, c0, c1)."""
+        for nm, t in (("cu", cu), ("cv", cv), ("juu", juu), ("juv", juv), ("jvu", jvu), ("jvv", jvv)):
+            self._vec(t, nm)
+        self._mask(dir_mask)
+        c0, c1 = (self.ex_begin, self.ex_end) if cols is None else (int(cols[0]), int(cols[1]))
+        if not self.ex_begin <= c0 < c1 <= self.ex_end:
+            raise ValueError("cols must be a non-empty element-column range of the handle's strip")
+        d = _lib.SemVelocityDesc(float(c_mass), float(c_stiff), float(c_gradx), float(c_grady), _ptr(cu), _ptr(cv),
+                                 _ptr(juu), _ptr(juv), _ptr(jvu), _ptr(jvv), _ptr(dir_mask), int(dir_sides),
+                                 int(ncomp), c0, c1)
+        return d, c0, c1
+
+    def _check_blocks(self, blocks, want, empty_too=False):
+        """Every wanted block is a contiguous float64 device tensor of its size (empty_too: a block of size 0 also)."""
+        for nm, sz in want:
+            t = blocks.get(nm)
+            if (sz or empty_too) and (t is None or t.numel() != sz or t.dtype != torch.float64
+                                      or t.device != self.device or not t.is_contiguous()):
+                raise ValueError(f"block {nm} must be a contiguous float64 tensor of {sz} entries on {self.device}")
+
     def velocity_blocks(self, blocks, *, c_mass=0.0, c_stiff=0.0, c_gradx=0.0, c_grady=0.0, cu=None, cv=None,
                         juu=None, juv=None, jvu=None, jvv=None, dir_mask=None, dir_sides=0, ncomp=2, cols=None,
                         stream=None):
@@ -200,25 +213,13 @@ class Mesh:
         sem_velocity_blocks) into `blocks` (VelocityJacobianSolver.empty_blocks layout); ncomp=1:
         the scalar operator A + diag(juu) alone.  cols=(c0, c1): blocks["AII"] holds the dense
         interiors of element columns [c0, c1) only."""
-        for nm, t in (("cu", cu), ("cv", cv), ("juu", juu), ("juv", juv), ("jvu", jvu), ("jvv", jvv)):
-            self._vec(t, nm)
-        if dir_mask is not None and (dir_mask.dtype != torch.uint8 or dir_mask.numel() != self.n_local):
-            raise ValueError("dir_mask must be a uint8 tensor of n_local entries")
+        d, c0, c1 = self._velocity_desc(c_mass, c_stiff, c_gradx, c_grady, cu, cv, juu, juv, jvu, jvv, dir_mask,
+                                        dir_sides, ncomp, cols)
         sizes = (C.c_int64 * 6)()
         _lib.check(self._lib.sem_line_block_sizes(self._h, int(ncomp), sizes))
         names = ("AII", "D", "aIB", "aBI", "E", "F")
-        c0, c1 = (self.ex_begin, self.ex_end) if cols is None else (int(cols[0]), int(cols[1]))
-        if not self.ex_begin <= c0 < c1 <= self.ex_end:
-            raise ValueError("cols must be a non-empty element-column range of the handle's strip")
         sizes[0] = sizes[0] // (self.ex_end - self.ex_begin) * (c1 - c0)
-        for nm, sz in zip(names, sizes):
-            t = blocks.get(nm)
-            if sz and (t is None or t.numel() != sz or t.dtype != torch.float64 or t.device != self.device
-                       or not t.is_contiguous()):
-                raise ValueError(f"block {nm} must be a contiguous float64 tensor of {sz} entries on {self.device}")
-        d = _lib.SemVelocityDesc(float(c_mass), float(c_stiff), float(c_gradx), float(c_grady), _ptr(cu), _ptr(cv),
-                                 _ptr(juu), _ptr(juv), _ptr(jvu), _ptr(jvv), _ptr(dir_mask), int(dir_sides),
-                                 int(ncomp), c0, c1)
+        self._check_blocks(blocks, zip(names, sizes))
         _lib.check(self._lib.sem_velocity_blocks(self._h, C.byref(d), *(_ptr(blocks.get(nm)) for nm in names),
                                                  self.stream_ptr(stream)))
         return blocks
@@ -229,28 +230,16 @@ class Mesh:
         """The velocity (ncomp=2) or scalar (ncomp=1) Jacobian in the nested condensation's layout
         (include/sem_ops.h, sem_condensed_blocks, ABI 7): blocks["Aii", "Aie", "Aei", "Aed", "Aeu", "Ael"]
         hold element columns cols = (c0, c1); "D", "aIB", "aBI", "E", "F" the whole mesh's interface pieces."""
-        for nm, t in (("cu", cu), ("cv", cv), ("juu", juu), ("juv", juv), ("jvu", jvu), ("jvv", jvv)):
-            self._vec(t, nm)
-        if dir_mask is not None and (dir_mask.dtype != torch.uint8 or dir_mask.numel() != self.n_local):
-            raise ValueError("dir_mask must be a uint8 tensor of n_local entries")
-        c0, c1 = (self.ex_begin, self.ex_end) if cols is None else (int(cols[0]), int(cols[1]))
-        if not self.ex_begin <= c0 < c1 <= self.ex_end:
-            raise ValueError("cols must be a non-empty element-column range of the handle's strip")
+        d, c0, c1 = self._velocity_desc(c_mass, c_stiff, c_gradx, c_grady, cu, cv, juu, juv, jvu, jvv, dir_mask,
+                                        dir_sides, ncomp, cols)
         line = (C.c_int64 * 6)()
         _lib.check(self._lib.sem_line_block_sizes(self._h, int(ncomp), line))
         cs = (C.c_int64 * 6)()
         _lib.check(self._lib.sem_condensed_block_sizes(self._h, int(ncomp), cs))
         cnames = ("Aii", "Aie", "Aei", "Aed", "Aeu", "Ael")
         lnames = ("D", "aIB", "aBI", "E", "F")
-        want = [(nm, cs[i] * (c1 - c0)) for i, nm in enumerate(cnames)] + list(zip(lnames, list(line)[1:]))
-        for nm, sz in want:
-            t = blocks.get(nm)
-            if t is None or t.numel() != sz or t.dtype != torch.float64 or t.device != self.device \
-                    or not t.is_contiguous():
-                raise ValueError(f"block {nm} must be a contiguous float64 tensor of {sz} entries on {self.device}")
-        d = _lib.SemVelocityDesc(float(c_mass), float(c_stiff), float(c_gradx), float(c_grady), _ptr(cu), _ptr(cv),
-                                 _ptr(juu), _ptr(juv), _ptr(jvu), _ptr(jvv), _ptr(dir_mask), int(dir_sides),
-                                 int(ncomp), c0, c1)
+        self._check_blocks(blocks, [(nm, cs[i] * (c1 - c0)) for i, nm in enumerate(cnames)]
+                           + list(zip(lnames, list(line)[1:])), empty_too=True)
         _lib.check(self._lib.sem_condensed_blocks(self._h, C.byref(d), *(_ptr(blocks[nm]) for nm in cnames + lnames),
                                                   self.stream_ptr(stream)))
         return blocks
@@ -276,27 +265,9 @@ class Mesh:
         u, v, ru, rv are plain vectors or (NX, NY) line views sharing one row stride (the velocity
         solve's interleaved [u | v] lines); a None output is not computed.  Every other operand is a plain
         vector: cu may be u itself (cv: v) only when u, v are plain vectors too (ValueError otherwise)."""
-        pitch = set()
-        views = []
-        for nm, t in (("u", u), ("v", v), ("ru", ru), ("rv", rv)):
-            t, s = self._line_view(t, nm)
-            views.append(t)
-            if t is not None:
-                pitch.add(s)
-        if len(pitch) > 1:
-            raise ValueError("u, v, ru, rv must share one layout")
-        for nm, t in (("p", p), ("rc", rc), ("T", T), ("cu", cu), ("cv", cv), ("juu", juu), ("juv", juv),
-                      ("jvu", jvu), ("jvv", jvv), ("dval_u", dval_u), ("dval_v", dval_v)):
-            self._vec(t, nm)
-        if dir_mask is not None and (dir_mask.dtype != torch.uint8 or dir_mask.numel() != self.n_local):
-            raise ValueError("dir_mask must be a uint8 tensor of n_local entries")
-        d = _lib.SemNsDesc(float(c_mass), float(c_stiff), float(c_gradx), float(c_grady), _ptr(cu), _ptr(cv),
-                           _ptr(juu), _ptr(juv), _ptr(jvu), _ptr(jvv), float(c_T), _ptr(T), float(c_div),
-                           _ptr(dval_u), _ptr(dval_v), _ptr(dir_mask), int(dir_sides), int(bool(pin_first)), int(pin),
-                           float(pin_val), pitch.pop() if pitch else 0)
-        _lib.check(self._lib.sem_ns_apply(self._h, C.byref(d), *(_ptr(t) for t in views[:2]), _ptr(p),
-                                          *(_ptr(t) for t in views[2:]), _ptr(rc), self.stream_ptr(stream)))
-        return views[2], views[3], rc
+        return self._ns_launch(self._lib.sem_ns_apply, ("u", "v", "p", "ru", "rv", "rc"), u, v, p, ru, rv, (rc,),
+                               c_mass, c_stiff, c_gradx, c_grady, cu, cv, juu, juv, jvu, jvv, c_T, T, c_div, dval_u,
+                               dval_v, dir_mask, dir_sides, pin, pin_val, pin_first, stream)
 
     def ns_apply_transpose(self, zu=None, zv=None, zc=None, yu=None, yv=None, yp=None, yT=None, *, c_mass=0.0,
                            c_stiff=0.0, c_gradx=0.0, c_grady=0.0, cu=None, cv=None, juu=None, juv=None, jvu=None,
@@ -307,9 +278,9 @@ class Mesh:
         yu, yv are plain vectors or (NX, NY) line views sharing one row stride; a None input is zeros, a None output
         is not computed.  Whole-mesh handles only.  T, dval_u, dval_v and pin_val are the descriptor fields the
         transpose of the linear part does not take: the library refuses them as the header documents."""
-        return self._ns_transpose(self._lib.sem_ns_apply_transpose, zu, zv, zc, yu, yv, yp, yT, c_mass, c_stiff,
-                                  c_gradx, c_grady, cu, cv, juu, juv, jvu, jvv, c_T, T, c_div, dval_u, dval_v, dir_mask,
-                                  dir_sides, pin, pin_val, pin_first, stream)
+        return self._ns_launch(self._lib.sem_ns_apply_transpose, _NS_T_NAMES, zu, zv, zc, yu, yv, (yp, yT), c_mass,
+                               c_stiff, c_gradx, c_grady, cu, cv, juu, juv, jvu, jvv, c_T, T, c_div, dval_u, dval_v,
+                               dir_mask, dir_sides, pin, pin_val, pin_first, stream)
 
     def ns_apply_transpose_part(self, zu=None, zv=None, zc=None, yu=None, yv=None, yp=None, yT=None, *, c_mass=0.0,
                                 c_stiff=0.0, c_gradx=0.0, c_grady=0.0, cu=None, cv=None, juu=None, juv=None, jvu=None,
@@ -322,36 +293,37 @@ class Mesh:
         shared lines (the forward exchange) gives the whole mesh's A^T z; z must agree on shared lines.  Line views
         hold the handle's own lines; `pin` stays a global node index.  On a whole-mesh handle: bitwise
         ns_apply_transpose."""
-        return self._ns_transpose(self._lib.sem_ns_apply_transpose_part, zu, zv, zc, yu, yv, yp, yT, c_mass, c_stiff,
-                                  c_gradx, c_grady, cu, cv, juu, juv, jvu, jvv, c_T, T, c_div, dval_u, dval_v, dir_mask,
-                                  dir_sides, pin, pin_val, pin_first, stream,
-                                  lines=int(self.line_end - self.line_begin + 1))
+        return self._ns_launch(self._lib.sem_ns_apply_transpose_part, _NS_T_NAMES, zu, zv, zc, yu, yv, (yp, yT), c_mass,
+                               c_stiff, c_gradx, c_grady, cu, cv, juu, juv, jvu, jvv, c_T, T, c_div, dval_u, dval_v,
+                               dir_mask, dir_sides, pin, pin_val, pin_first, stream,
+                               lines=int(self.line_end - self.line_begin + 1))
 
-    def _ns_transpose(self, entry, zu, zv, zc, yu, yv, yp, yT, c_mass, c_stiff, c_gradx, c_grady, cu, cv, juu, juv, jvu,
-                      jvv, c_T, T, c_div, dval_u, dval_v, dir_mask, dir_sides, pin, pin_val, pin_first, stream,
-                      lines=None):
-        """The checks and the descriptor of the two transposed Navier-Stokes entry points."""
+    def _ns_launch(self, entry, names, u, v, p, ru, rv, tail, c_mass, c_stiff, c_gradx, c_grady, cu, cv, juu, juv, jvu,
+                   jvv, c_T, T, c_div, dval_u, dval_v, dir_mask, dir_sides, pin, pin_val, pin_first, stream,
+                   lines=None):
+        """The checks, the SemNsDesc and the launch of the three Navier-Stokes entry points: entry(u, v, p, ru, rv,
+        *tail) with `names` the operands' names in that order; u, v, ru, rv may be line views, the rest are plain
+        vectors.  Returns (ru, rv, *tail)."""
         pitch = set()
         views = []
-        for nm, t in (("zu", zu), ("zv", zv), ("yu", yu), ("yv", yv)):
+        for nm, t in zip(names[:2] + names[3:5], (u, v, ru, rv)):
             t, s = self._line_view(t, nm, lines)
             views.append(t)
             if t is not None:
                 pitch.add(s)
         if len(pitch) > 1:
-            raise ValueError("zu, zv, yu, yv must share one layout")
-        for nm, t in (("zc", zc), ("yp", yp), ("yT", yT), ("T", T), ("cu", cu), ("cv", cv), ("juu", juu), ("juv", juv),
-                      ("jvu", jvu), ("jvv", jvv), ("dval_u", dval_u), ("dval_v", dval_v)):
+            raise ValueError(f"{', '.join(names[:2] + names[3:5])} must share one layout")
+        for nm, t in ((names[2], p), *zip(names[5:], tail), ("T", T), ("cu", cu), ("cv", cv), ("juu", juu),
+                      ("juv", juv), ("jvu", jvu), ("jvv", jvv), ("dval_u", dval_u), ("dval_v", dval_v)):
             self._vec(t, nm)
-        if dir_mask is not None and (dir_mask.dtype != torch.uint8 or dir_mask.numel() != self.n_local):
-            raise ValueError("dir_mask must be a uint8 tensor of n_local entries")
+        self._mask(dir_mask)
         d = _lib.SemNsDesc(float(c_mass), float(c_stiff), float(c_gradx), float(c_grady), _ptr(cu), _ptr(cv),
                            _ptr(juu), _ptr(juv), _ptr(jvu), _ptr(jvv), float(c_T), _ptr(T), float(c_div),
                            _ptr(dval_u), _ptr(dval_v), _ptr(dir_mask), int(dir_sides), int(bool(pin_first)), int(pin),
                            float(pin_val), pitch.pop() if pitch else 0)
-        _lib.check(entry(self._h, C.byref(d), *(_ptr(t) for t in views[:2]), _ptr(zc), *(_ptr(t) for t in views[2:]),
-                         _ptr(yp), _ptr(yT), self.stream_ptr(stream)))
-        return views[2], views[3], yp, yT
+        _lib.check(entry(self._h, C.byref(d), *(_ptr(t) for t in views[:2]), _ptr(p), *(_ptr(t) for t in views[2:]),
+                         *(_ptr(t) for t in tail), self.stream_ptr(stream)))
+        return (views[2], views[3], *tail)
 
     # ------------------------------------------------------------------ host-side 1-D tables
     def weights_1d(self):
@@ -368,6 +340,15 @@ def _assembled_diag(vals, P, e_lo, e_hi, g_lo, g_hi):
     for e in range(e_lo, e_hi):
         out[e * P - g_lo: e * P + P + 1 - g_lo] += vals
     return out
+
+
+def mass_diagonal(P, nex, ney, dx, dy):
+    """Diagonal of the whole mesh's assembled mass matrix (SEM.py:170-183): (dx/2)(dy/2) wx_g wy_g with the GLL
+    weights summed over the elements holding each 1-D node (Mesh.weights_1d's sums, without a handle)."""
+    from . import GLL
+    w = GLL.standard_nodes(P)[1]
+    wx, wy = _assembled_diag(w, P, 0, nex, 0, nex * P), _assembled_diag(w, P, 0, ney, 0, ney * P)
+    return ((dx / 2) * (dy / 2)) * np.outer(wx, wy).ravel()
 
 
 _MESHES = {}

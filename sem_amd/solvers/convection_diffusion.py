@@ -25,8 +25,6 @@ preconditioning leaves the stopping test on the true residual ||dres_op(dT) -
 dres||_2, so the reference's rule is unchanged; the Krylov count drops from
 hundreds-thousands of matvecs to one or two.
 """
-import typing
-
 import numpy as np
 import scipy.sparse.linalg as linalg
 import torch
@@ -35,6 +33,7 @@ from .. import SEM, _lib
 from ..device import get_mesh
 from ..krylov import Recycle, gcro, gmres
 from ..operators import ConvectionTensor, SEMOperator
+from ._base import SolverBase
 from .velocity_solve import VelocityJacobianSolver
 
 
@@ -85,7 +84,9 @@ class DirichletRows:
         return dict(dir_sides=self.sides, dir_mask=self.mask)
 
 
-class ConvectionDiffusionSolver:
+class ConvectionDiffusionSolver(SolverBase):
+    _name = "ConvectionDiffusion"
+
     def __init__(self, L_x: float, L_y: float, Pe: float, P: int, N_ex: int, N_ey: int,
                  T_W: float = None, T_E: float = None, T_S: float = None, T_N: float = None,
                  mtol=1e-7, iprint: list = [], krylov: str = "device", max_basis: int = 2000,  # noqa: B006
@@ -114,16 +115,11 @@ class ConvectionDiffusionSolver:
             raise ValueError("precond must be 'condensed' or None")
         # a partitioned solver preconditions with the element-partitioned condensation (strip_solve.py)
         self._precond = precond
-        if partition_update not in ("distributed", "central"):
-            raise ValueError("partition_update must be 'distributed' or 'central'")
-        self._partition_update = partition_update
-        self._partition_adjoint = bool(partition_adjoint)
+        super().__init__(partition, partition_update, partition_adjoint)
         self._args = dict(L_x=L_x, L_y=L_y, Pe=Pe, P=P, N_ex=N_ex, N_ey=N_ey, T_W=T_W, T_E=T_E, T_S=T_S, T_N=T_N,
                           mtol=mtol, iprint=iprint, max_basis=max_basis, precond=precond)
-        self._twin, self._sys_uv, self._twin_stale = None, None, True
         self._factor = None     # condensed Jacobian of the current Sys (rebuilt after _get_residuals)
         self._krylov, self._max_basis = krylov, max_basis
-        self._part = partition
         # recycled Krylov subspace across _get_update calls with one operator (sem_amd.krylov.Recycle):
         # the Boussinesq coupler's block-Jacobi preconditioner solves with the same Sys tens of times
         self._recycle_bytes, self._recycle = recycle_bytes, None
@@ -151,7 +147,6 @@ class ConvectionDiffusionSolver:
         self._Sys = None
         self._Jac_T_u = None
         self._Jac_T_v = None
-        self._free = None       # 1 - Dirichlet mask as a device vector (_get_dresiduals_T)
 
         # Dirichlet values and mask (ConvectionDiffusion_Solver.py:62-71)
         self._dirichlet = np.full(self.N, np.nan)
@@ -165,22 +160,6 @@ class ConvectionDiffusionSolver:
         self._dir = DirichletRows(self._mesh, self._mask_dir, sides)
         self._dir_val = self._dev(np.where(self._mask_dir, self._dirichlet, 0.0))
 
-    # ------------------------------------------------------------------ helpers
-    def _dev(self, a):
-        """Device vector of this solver's (local) DOFs; a global NumPy vector is sliced to the strip."""
-        if a is None:
-            return None
-        if self._part is not None and not isinstance(a, torch.Tensor):
-            a = self._part.local(np.asarray(a))
-        return self._mesh.to_device(a)
-
-    def _out(self, y, like):
-        if isinstance(like, torch.Tensor):
-            return y
-        if self._part is not None:
-            y = self._part.gather(y)
-        return y.cpu().numpy()
-
     # ------------------------------------------------------------------ reference methods
     def _get_residuals(self, T, u, v):
         """res = Sys T, Dirichlet rows T - T_dir (ConvectionDiffusion_Solver.py:73-92)."""
@@ -188,16 +167,12 @@ class ConvectionDiffusionSolver:
         self._Sys = Conv + self._K
         self._factor = None
         if self._part is not None:
-            self._sys_uv, self._twin_stale = (self._dev(u), self._dev(v)), True
+            self._twin_lin, self._twin_stale = (self._dev(u), self._dev(v)), True
         if self._recycle is not None:   # the update operator depends on Sys
             self._recycle.reset()
         y = self._apply(self._dev(T), dir_mode=_lib.DIR_IDENTITY, dir_val=self._dir_val, **self._sys_kw(),
                         **self._dir.kw())
         return self._out(y, T)
-
-    def _sys_kw(self):
-        cX, cu, cY, cv, d = self._Sys._coeffs()
-        return dict(c_stiff=self._Sys.cK, c_mass=self._Sys.cM, c_gradx=cX, cu=cu, c_grady=cY, cv=cv)
 
     def _calc_jacobians(self, T):
         """Pe diag(G_x T), Pe diag(G_y T) (ConvectionDiffusion_Solver.py:94-102)."""
@@ -219,29 +194,6 @@ class ConvectionDiffusionSolver:
         y = self._apply(self._dev(dT), dir_mode=_lib.DIR_IDENTITY, **self._sys_kw(), **self._dir.kw(), **kw)
         return self._out(y, dT)
 
-    def _whole_mesh_only(self, what, adjoint=False):
-        """Refuse `what` on a partitioned solver; adjoint=True: unless partition_adjoint opted in."""
-        if self._part is not None and not (adjoint and getattr(self, "_partition_adjoint", False)):
-            raise ValueError(f"ConvectionDiffusion: {what} is implemented for whole-mesh solvers only" +
-                             (" unless the partitioned solver was built with partition_adjoint=True" if adjoint else ""))
-
-    def _operator(self, x, c_mass=0.0, c_stiff=0.0, cu=None, cv=None, free=False):
-        """(c_mass M + c_stiff K + diag(cu) G_x + diag(cv) G_y) x on this solver's mesh in one fused launch, no
-        row replaced; free=True zeroes the Dirichlet rows.  What the coupler's parameter partials and the
-        functionals (solvers/functionals.py) are built from.  NumPy in, NumPy out; device tensors likewise."""
-        self._whole_mesh_only("_operator")
-        kw = {}
-        if cu is not None:
-            kw.update(c_gradx=1.0, cu=self._dev(cu))
-        if cv is not None:
-            kw.update(c_grady=1.0, cv=self._dev(cv))
-        y = self._mesh.apply(self._dev(x), c_mass=c_mass, c_stiff=c_stiff, **kw)
-        if free:
-            if self._free is None:   # 1 - m on the device
-                self._free = self._mesh.to_device((~self._dir.mask_np).astype(np.float64))
-            y = self._free * y
-        return self._out(y, x)
-
     def _apply_T(self, w, y=None, **kw):
         """A_D^T w: one fused transposed launch of Sys with identity Dirichlet rows; on a partitioned solver
         the transposed strip apply with the interface exchange (partition.step_T; w agrees on shared lines)."""
@@ -261,9 +213,7 @@ class ConvectionDiffusionSolver:
             raise RuntimeError("ConvectionDiffusion: _get_residuals and _calc_jacobians must run before "
                                "_get_dresiduals_T")
         w = self._dev(dres_bar)
-        if self._free is None:   # 1 - m on the device
-            self._free = self._mesh.to_device((~self._dir.mask_np).astype(np.float64))
-        wf = self._free * w
+        wf = self._free_rows() * w
         out = (self._apply_T(w), self._Jac_T_u._coeffs()[4] * wf, self._Jac_T_v._coeffs()[4] * wf)
         return tuple(self._out(y, dres_bar) for y in out)
 
@@ -282,34 +232,17 @@ class ConvectionDiffusionSolver:
         self._whole_mesh_only("_get_update_T", adjoint=True)
         if self._Sys is None:
             raise RuntimeError("ConvectionDiffusion: _get_residuals must run before _get_update_T")
-        b = self._dev(dT_bar)
-        x0 = self._dev(dres0)
-        it = [0]
-
-        def cb(est):
-            it[0] += 1
-            if "LGMRES_iter" in self._iprint:
-                print(f"ConvectionDiffusion adjoint GMRES: {it[0]}\t{est}", flush=True)
-
-        restart = max(1, min(int(self.N * 0.3), self._max_basis))
-        kw = {}
+        kw, precond = {}, None
         if self._part is not None:
             kw = dict(inner=self._part.inner)
         elif self._precond == "condensed":
             vs = self._jacobian_solver()
             if vs.device.type == "cuda" and vs._graph_T is None:
                 vs.capture_T()
-            kw = dict(precond=vs.solve1_T)
-            restart = min(restart, 100)
-        r = gmres(lambda v: self._apply_T(v), b, x0=x0, atol=self._mtol * np.sqrt(self.N), rtol=0.0, restart=restart,
-                  maxiter=10 * self.N, callback=cb, **kw)
-        if r.info != 0:
-            raise RuntimeError(f"ConvectionDiffusion LGMRES: Failed to converge in {r.info} iterations")
-        self.matvecs = r.matvecs
-        if "LGMRES_suc" in self._iprint:
-            res = (self._apply_T(r.x) - b).abs().max().item()
-            print(f"ConvectionDiffusion adjoint GMRES: Converged in {r.matvecs} evaluations with max-norm {res}")
-        return self._out(r.x, dT_bar)
+            precond = vs.solve1_T
+        x = self._krylov_solve(gmres, lambda v: self._apply_T(v), self._dev(dT_bar), self._dev(dres0), precond,
+                               "adjoint GMRES", progress=False, maxiter=10 * self.N, **kw)
+        return self._out(x, dT_bar)
 
     def _get_update(self, dres, dT0=None):
         """Newton update: solve dres_op(dT) = dres (ConvectionDiffusion_Solver.py:123-156)."""
@@ -345,89 +278,67 @@ class ConvectionDiffusionSolver:
             self._factor = vs
         return self._factor
 
-    def _get_update_device(self, dres, dT0=None):
-        """GMRES with the Krylov basis in HBM; restart = min(int(0.3 N), max_basis) (the
-        reference's inner_m, capped so the basis fits device memory), right-preconditioned by the
-        condensed direct solve when precond="condensed"."""
-        b = self._dev(dres)
-        x0 = self._dev(dT0)
-        it = [0]
+    def _restart(self, precond):
+        """restart = min(int(0.3 N), max_basis) (the reference's inner_m, capped so the basis fits device memory), at
+        most 100 under a preconditioner; from the global N, so the same on every rank."""
+        restart = max(1, min(int(self.N * 0.3), self._max_basis))
+        return restart if precond is None else min(restart, 100)
 
-        prog = getattr(self, "_progress", 0)
+    def _krylov_solve(self, krylov, matvec, b, x0, precond, label, progress, **kw):
+        """The device Krylov solve of _get_update_device and _get_update_T: `krylov` (gcro or gmres) with the basis in
+        HBM, the reference's stopping rule atol = mtol sqrt(N), _restart's restart, the iteration callback (progress:
+        honouring the _progress hook), the convergence check, self.matvecs and the LGMRES_suc report."""
+        it = [0]
+        prog = self._progress if progress else 0
 
         def cb(est):
             it[0] += 1
             if "LGMRES_iter" in self._iprint or (prog and it[0] % prog == 0):
-                print(f"ConvectionDiffusion GMRES: {it[0]}\t{est}", flush=True)
+                print(f"ConvectionDiffusion {label}: {it[0]}\t{est}", flush=True)
 
-        restart = max(1, min(int(self.N * 0.3), self._max_basis))
-        precond = None
-        if self._precond == "condensed" and (self._part is None or self._P > 1):
-            precond = self._jacobian_solver().solve1
-            restart = min(restart, 100)
-        if self._part is not None:
-            r = gmres(lambda v: self._get_dresiduals(v), b, x0=x0, atol=self._mtol * np.sqrt(self.N), rtol=0.0,
-                      restart=restart, maxiter=10 * self.N, precond=precond, callback=cb, inner=self._part.inner)
-        else:
-            if self._recycle_bytes and self._recycle is None:
-                n = self._mesh.n_local
-                cap = min(n, max(restart + 1, int(self._recycle_bytes // (16 * n))))
-                self._recycle = Recycle(n, torch.float64, self._mesh.device, cap)
-            r = gcro(lambda v: self._get_dresiduals(v), b, x0=x0, atol=self._mtol * np.sqrt(self.N), rtol=0.0,
-                     restart=restart, precond=precond, callback=cb,
-                     recycle=self._recycle if precond is None else None)
+        r = krylov(matvec, b, x0=x0, atol=self._mtol * np.sqrt(self.N), rtol=0.0, restart=self._restart(precond),
+                   precond=precond, callback=cb, **kw)
         if r.info != 0:
             raise RuntimeError(f"ConvectionDiffusion LGMRES: Failed to converge in {r.info} iterations")
         self.matvecs = r.matvecs
         if "LGMRES_suc" in self._iprint:
-            res = (self._get_dresiduals(r.x) - b).abs().max().item()
-            print(f"ConvectionDiffusion GMRES: Converged in {r.matvecs} evaluations with max-norm {res}")
-        return self._out(r.x, dres)
+            res = (matvec(r.x) - b).abs().max().item()
+            print(f"ConvectionDiffusion {label}: Converged in {r.matvecs} evaluations with max-norm {res}")
+        return r.x
+
+    def _get_update_device(self, dres, dT0=None):
+        """GMRES with the Krylov basis in HBM (_krylov_solve), right-preconditioned by the condensed direct solve
+        when precond="condensed": over the strips the GMRES with all-reduced inner products, on the whole mesh GCRO
+        (recycling, when asked for, only without the preconditioner)."""
+        precond = None
+        if self._precond == "condensed" and (self._part is None or self._P > 1):
+            precond = self._jacobian_solver().solve1
+        if self._part is not None:
+            krylov, kw = gmres, dict(maxiter=10 * self.N, inner=self._part.inner)
+        else:
+            if self._recycle_bytes and self._recycle is None:
+                n = self._mesh.n_local
+                cap = min(n, max(self._restart(precond) + 1, int(self._recycle_bytes // (16 * n))))
+                self._recycle = Recycle(n, torch.float64, self._mesh.device, cap)
+            krylov, kw = gcro, dict(recycle=self._recycle if precond is None else None)
+        x = self._krylov_solve(krylov, lambda v: self._get_dresiduals(v), self._dev(dres), self._dev(dT0), precond,
+                               "GMRES", progress=True, **kw)
+        return self._out(x, dres)
 
     def _central_solver(self):
         """Rank 0's whole-mesh counterpart for partition_update="central" (same arguments, no
         partition)."""
         return ConvectionDiffusionSolver(**self._args)
 
-    def _global(self, a):
-        if isinstance(a, torch.Tensor):
-            return self._part.gather(a).cpu().numpy()
-        return np.asarray(a, dtype=np.float64)
-
     def _get_update_central(self, dres, dT0=None):
-        """The partitioned solver's update on rank 0's whole-mesh counterpart: its Sys is set from
-        the gathered velocity field of the last _get_residuals (the reference interface), it solves
-        with the condensed direct preconditioner, and the update is broadcast to every rank."""
-        part = self._part
-        if self._sys_uv is None:
+        """The partitioned solver's update on rank 0's whole-mesh counterpart (SolverBase._central): its Sys is set
+        from the gathered velocity field of the last _get_residuals (the reference interface), it solves with the
+        condensed direct preconditioner, and the update is broadcast to every rank."""
+        if self._twin_lin is None:
             raise RuntimeError("ConvectionDiffusion: _get_residuals must run before _get_update")
-        stale = self._twin_stale
-        if stale:
-            u, v = (self._global(a) for a in self._sys_uv)
-            self._twin_stale = False
-        b = self._global(dres)
-        x0 = None if dT0 is None else self._global(dT0)
-        out = torch.zeros(self.N + 1, dtype=torch.float64)
-        err = None
-        if part.rank == 0:
-            try:   # a rank-0 failure is broadcast as a NaN status: every rank raises, none waits
-                if stale:
-                    if self._twin is None:
-                        self._twin = self._central_solver()
-                    self._twin._get_residuals(np.zeros(self.N), u, v)
-                out[:self.N] = torch.from_numpy(np.asarray(self._twin._get_update(b, dT0=x0)))
-                out[-1] = float(getattr(self._twin, "matvecs", -1))
-            except (RuntimeError, ValueError) as e:
-                err = e
-                out[-1] = float("nan")
-        out = part.broadcast(out)
-        if err is not None:
-            raise err
-        if torch.isnan(out[-1]):
-            raise RuntimeError("ConvectionDiffusion: the update failed on rank 0 (see its error)")
-        self.matvecs = int(out[-1].item())
-        dT = out[:self.N].cpu().numpy()
-        return self._dev(dT) if isinstance(dres, torch.Tensor) else dT
+        return self._central(lambda twin, u, v: twin._get_residuals(np.zeros(self.N), u, v),
+                             lambda twin, b, x0: (twin._get_update(b, dT0=x0),), (dres, dT0), 1, "matvecs",
+                             "the update")[0]
 
     def _get_update_scipy(self, dres, dT0=None):
         """The reference's LGMRES on the host around device matvecs."""
@@ -466,13 +377,6 @@ class ConvectionDiffusionSolver:
         res = self._get_residuals(T, u, v)
         dT = self._get_update(-res)
         return T + dT
-
-    def _get_vector(self, f_func: typing.Callable[[np.ndarray, np.ndarray], np.ndarray]) -> np.ndarray:
-        return f_func(self.points[0], self.points[1])
-
-    def _get_interpol(self, f, points_plot):
-        f_e = SEM.scatter(f, self._P, self._N_ex, self._N_ey)
-        return SEM.eval_interpolation(f_e, self.points_e, points_plot)
 
     def run(self, u_func, v_func, points_plot):
         u = self._get_vector(u_func)

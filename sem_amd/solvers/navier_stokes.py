@@ -19,37 +19,46 @@ instead of host SuperLU, and the Schur system runs the device GMRES.  No CSR mat
 import gc
 import os
 import time
+import typing
 
 import numpy as np
 import torch
 
 from .. import SEM, _lib
-from ..device import capture_graph, get_mesh, no_gc
+from ..device import capture_graph, get_mesh, mass_diagonal, no_gc
 from ..krylov import Recycle, gcro, gmres
 from ..operators import ConvectionTensor, SEMOperator
 from ..tracing import phase
+from ._base import SolverBase
 from .convection_diffusion import DirichletRows
 from .nested_dissection import NestedDissectionSolver
 from .velocity_solve import VelocityJacobianSolver
 
 
-def _mass_diagonal(P, nex, ney, dx, dy):
-    """Diagonal of the assembled mass matrix (SEM.py:170-183): (dx/2)(dy/2) wx_g wy_g with the GLL
-    weights summed over the elements holding each 1-D node."""
-    from .. import GLL
-    w = GLL.standard_nodes(P)[1]
-    wx, wy = np.zeros(nex * P + 1), np.zeros(ney * P + 1)
-    for e in range(nex):
-        wx[e * P:e * P + P + 1] += w
-    for e in range(ney):
-        wy[e * P:e * P + P + 1] += w
-    return ((dx / 2) * (dy / 2)) * np.outer(wx, wy).ravel()
-
-
 _ALL_SIDES = _lib.SIDE_W | _lib.SIDE_E | _lib.SIDE_S | _lib.SIDE_N
 
 
-class NavierStokesSolver:
+class _SchurVariant(typing.NamedTuple):
+    """What distinguishes the pressure-Schur eliminations that NavierStokesSolver._schur_update runs."""
+    name: str                       # the Krylov solve in the progress and success messages
+    fail: str                       # ... and in the non-convergence error
+    solve: typing.Callable          # (bu, bv) -> (xu, xv): the velocity solve, J^-1 or J^-T
+    pressure_rhs: typing.Callable   # (fu, fv, c0): the launch that writes what the Schur right-hand side subtracts
+    velocity_rhs: typing.Callable   # (p, bu, bv) -> the final velocity solve's right-hand sides (one launch)
+    slot: str                       # the attribute that caches the Schur operator ("_schur" / "_schur_T")
+    operator: typing.Callable       # () -> the Schur operator
+    precond: typing.Callable        # the right preconditioner
+    size: int                       # the vector length that sets the restart (_restart)
+    krylov: typing.Callable         # gcro or gmres
+    kw: typing.Callable             # restart -> the call's further keywords
+    progress: bool                  # honour the _progress hook
+    clock: bool                     # progress lines carry the elapsed time
+    report: bool                    # print the LGMRES_suc line
+
+
+class NavierStokesSolver(SolverBase):
+    _name, _whole_mesh_note = "NavierStokes", " (no transposed strip solve)"
+
     def __init__(self, L_x: float, L_y: float, Re: float, Gr: float, P: int, N_ex: int, N_ey: int,
                  v_W: float = 0, v_E: float = 0, u_S: float = 0, u_N: float = 0,
                  mtol=1e-7, mtol_newton=1e-5, iprint: list = ['NEWTON_suc', 'NEWTON_iter'],  # noqa: B006
@@ -99,12 +108,9 @@ class NavierStokesSolver:
             raise ValueError("schur_precond must be 'mass' or 'pcd'")
         if velocity_interior not in ("auto", "nd", "nested", "lu", "inverse"):
             raise ValueError("velocity_interior must be 'auto', 'nd', 'nested', 'lu' or 'inverse'")
-        if partition_update not in ("distributed", "central"):
-            raise ValueError("partition_update must be 'distributed' or 'central'")
+        super().__init__(partition, partition_update, partition_adjoint)
         if partition is not None and schur_precond != "mass" and partition_update == "distributed":
             raise ValueError("the distributed update uses the mass-diagonal Schur preconditioner")
-        self._partition_update = partition_update
-        self._partition_adjoint = bool(partition_adjoint)
         self._schur_precond, self._Ap = schur_precond, None
         self._iprint = iprint
         self._recycle_bytes, self._schur_recycle = recycle_bytes, None
@@ -128,7 +134,7 @@ class NavierStokesSolver:
                           u_N=u_N, mtol=mtol, mtol_newton=mtol_newton, iprint=iprint, max_basis=max_basis,
                           velocity_interior=velocity_interior, velocity_graph=velocity_graph,
                           recycle_bytes=recycle_bytes, velocity_sweep=velocity_sweep, schur_precond=schur_precond)
-        self._part, self._twin, self._lin, self._lin_sys = partition, None, None, None
+        self._lin_sys = None
         if partition is None:
             self._mesh = m = get_mesh(P, N_ex, N_ey, dx, dy)
             self._M = SEM.global_mass_matrix(P, N_ex, N_ey, dx, dy)
@@ -169,9 +175,10 @@ class NavierStokesSolver:
         if partition is not None:
             # the reference's mass diagonal (NavierStokes_Solver.py:207-212) is the assembled one: on a
             # shared line both strips hold the whole-mesh value
-            self._Mdiag = m.to_device(partition.local(_mass_diagonal(P, N_ex, N_ey, dx, dy)))
+            self._Mdiag = m.to_device(partition.local(mass_diagonal(P, N_ex, N_ey, dx, dy)))
             self._pin_local = self._pin - m.dof_begin if 0 <= self._pin - m.dof_begin < m.n_local else -1
             return
+        self._pin_local = self._pin
         self._Mdiag = m.to_device(self._M.diagonal())
         # PCD row weights: 1/M on the continuity rows, 0 on the replaced rows (and the reverse)
         repl = self._mask_bound.copy()
@@ -181,27 +188,6 @@ class NavierStokesSolver:
         self._pcd_b = m.to_device(repl.astype(np.float64))
 
     # ------------------------------------------------------------------ helpers
-    def _dev(self, a):
-        """Device vector of this solver's (local) DOFs; a global NumPy vector is sliced to the strip."""
-        if a is None:
-            return None
-        if self._part is not None and not isinstance(a, torch.Tensor):
-            a = self._part.local(np.asarray(a))
-        return self._mesh.to_device(a)
-
-    def _out(self, t, like):
-        if isinstance(like, torch.Tensor):
-            return t
-        if self._part is not None:
-            t = self._part.gather(t)
-        return t.cpu().numpy()
-
-    def _global(self, a):
-        """Global NumPy vector from a global NumPy vector or this rank's strip tensor."""
-        if isinstance(a, torch.Tensor) and self._part is not None:
-            return self._part.gather(a).cpu().numpy()
-        return np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
-
     def _norm(self, *ys):
         if self._part is not None:
             return self._part.norm(*ys)
@@ -218,10 +204,6 @@ class NavierStokesSolver:
             return self._mesh.apply(x, **{which: 1.0})
         return self._part.step(x, **{which: 1.0})
 
-    def _sys_kw(self, Sys):
-        cX, cu, cY, cv, d = Sys._coeffs()
-        return dict(c_stiff=Sys.cK, c_mass=Sys.cM, c_gradx=cX, cu=cu, c_grady=cY, cv=cv)
-
     def _ns_kw(self, pin_first):
         """Row replacements of sem_ns_apply: Dirichlet rows (mask_bound) and the pinned-pressure row."""
         return dict(pin=self._pin, pin_val=0.0 if not pin_first else self._pin_val, pin_first=pin_first,
@@ -237,7 +219,7 @@ class NavierStokesSolver:
         if self._schur_recycle is not None:   # the Schur operator depends on Sys
             self._schur_recycle.reset()
         ru, rv, rc = (torch.empty_like(U) for _ in range(3))
-        m.ns_apply(U, V, Pp, ru, rv, rc, **self._sys_kw(self._Sys), c_T=-self._Gr_over_Re, T=Tt,
+        m.ns_apply(U, V, Pp, ru, rv, rc, **self._sys_kw(), c_T=-self._Gr_over_Re, T=Tt,
                    dval_u=self._dval_u, dval_v=self._dval_v, **self._ns_kw(pin_first=True))
         if self._part is not None:
             self._part.assemble(ru, rv, rc)
@@ -260,8 +242,8 @@ class NavierStokesSolver:
             self._Jac_v_v = self._Sys + SEMOperator(m, dg=[(Re, self._grad(V, "c_grady"))])
             self._Jac_u_v = SEMOperator(m, dg=[(Re, self._grad(U, "c_grady"))])
             self._Jac_v_u = SEMOperator(m, dg=[(Re, self._grad(V, "c_gradx"))])
-            self._lin = {"sys": self._lin_sys, "jac": (U, V), "stale": True}
-        self._jac_kw = dict(self._sys_kw(self._Sys), juu=self._Jac_u_u._coeffs()[4], jvv=self._Jac_v_v._coeffs()[4],
+            self._twin_lin, self._twin_stale = self._lin_sys + (U, V), True
+        self._jac_kw = dict(self._sys_kw(), juu=self._Jac_u_u._coeffs()[4], jvv=self._Jac_v_v._coeffs()[4],
                             juv=self._Jac_u_v._coeffs()[4], jvu=self._Jac_v_u._coeffs()[4])
         self._velo = None  # factorised on first use, reused until the next linearisation
         self._schur = self._schur_T = None
@@ -284,50 +266,32 @@ class NavierStokesSolver:
         no partition)."""
         return NavierStokesSolver(**self._args)
 
+    def _twin_refresh(self, twin, us, vs, uj, vj):
+        """The gathered linearisation through the reference interface: _get_residuals sets Sys (the residual's
+        u, v), _calc_jacobians the Jacobians."""
+        z = np.zeros(self.N)
+        twin._get_residuals(us, vs, z, z)
+        twin._calc_jacobians(uj, vj)
+
     def _get_update_partitioned(self, dres_u, dres_v, dres_cont, du0, dv0, dp0):
-        """Whole-mesh update for a strip-partitioned solver: the linearisation (the residual's u, v for
-        Sys, the Jacobian's u, v) and the right-hand sides are gathered; rank 0 hands them to its
-        whole-mesh counterpart through the reference interface (_get_residuals sets Sys,
-        _calc_jacobians the Jacobians, _get_update solves) and broadcasts the update."""
-        part = self._part
-        lin = self._lin
-        if lin is None:
+        """Whole-mesh update for a strip-partitioned solver (SolverBase._central): the linearisation and the
+        right-hand sides are gathered, rank 0's whole-mesh counterpart runs _get_update, the update is broadcast."""
+        if self._twin_lin is None:
             raise RuntimeError("NavierStokes: _calc_jacobians must run before _get_update")
-        stale = lin.get("stale")
-        if stale:
-            us, vs = (self._global(a) for a in lin["sys"])
-            uj, vj = (self._global(a) for a in lin["jac"])
-            lin["stale"] = False
-        rhs = [self._global(a) for a in (dres_u, dres_v, dres_cont)]
-        x0 = [None if a is None else self._global(a) for a in (du0, dv0, dp0)]
-        out = torch.zeros(3 * self.N + 1, dtype=torch.float64)
-        err = None
-        if part.rank == 0:
-            # a failure on rank 0 (non-convergence, a singular block, out of memory) travels in the
-            # broadcast as a NaN status, so every rank raises instead of waiting in the collective
-            try:
-                if stale:
-                    if self._twin is None:
-                        self._twin = self._central_solver()
-                    z = np.zeros(self.N)
-                    self._twin._get_residuals(us, vs, z, z)
-                    self._twin._calc_jacobians(uj, vj)
-                d = self._twin._get_update(*rhs, du0=x0[0], dv0=x0[1], dp0=x0[2])
-                out[:3 * self.N] = torch.from_numpy(np.concatenate([np.asarray(a) for a in d]))
-                out[-1] = float(getattr(self._twin, "schur_matvecs", -1))
-            except (RuntimeError, ValueError) as e:
-                err = e
-                out[-1] = float("nan")
-        out = part.broadcast(out)
-        if err is not None:
-            raise err
-        if torch.isnan(out[-1]):
-            raise RuntimeError("NavierStokes: the update failed on rank 0 (see its error)")
-        self.schur_matvecs = int(out[-1].item())
-        d = [out[i * self.N:(i + 1) * self.N].cpu().numpy() for i in range(3)]
-        if isinstance(dres_u, torch.Tensor):
-            return tuple(self._dev(a) for a in d)
-        return tuple(d)
+        return self._central(self._twin_refresh,
+                             lambda twin, ru, rv, rc, u0, v0, p0: twin._get_update(ru, rv, rc, du0=u0, dv0=v0, dp0=p0),
+                             (dres_u, dres_v, dres_cont, du0, dv0, dp0), 3, "schur_matvecs", "the update")
+
+    def _get_update_T_partitioned(self, du_bar, dv_bar, dp_bar, dres_c0):
+        """_get_update_T of a strip-partitioned solver, run centrally whatever partition_update says (the mirror of
+        _get_update_partitioned on the same cached twin and the same staleness record).  This is the functional
+        path, not the scalable one: every call moves whole-mesh vectors through rank 0.  A distributed adjoint Schur
+        solve S^T q = E^T q - B^T J^-T C^T q needs the transposed strip solvers, which do not exist yet."""
+        if self._twin_lin is None:
+            raise RuntimeError("NavierStokes: _get_residuals and _calc_jacobians must run before _get_update_T")
+        return self._central(self._twin_refresh,
+                             lambda twin, bu, bv, bp, q0: twin._get_update_T(bu, bv, bp, dres_c0=q0),
+                             (du_bar, dv_bar, dp_bar, dres_c0), 3, "schur_matvecs", "the adjoint update")
 
     def _use_nd(self):
         """Nested dissection (velocity_interior "auto" / "nd") needs P >= 2 and the whole perimeter Dirichlet."""
@@ -381,55 +345,7 @@ class NavierStokesSolver:
         """_get_update (NavierStokes_Solver.py:162-236) on the strips: the element-partitioned velocity
         solve inside the Schur-complement GMRES, whose inner products are all-reduced (a shared line
         counted once); the reference's mass-diagonal preconditioner and stopping rule."""
-        vs = self._strip_velocity_solver()
-        m, part = self._mesh, self._part
-        kw = self._ns_kw(pin_first=False)
-        ru, rv, rc = self._dev(dres_u), self._dev(dres_v), self._dev(dres_cont)
-        fu, fv = vs.solve(ru, rv)
-        c0 = torch.empty_like(rc)
-        m.ns_apply(fu, fv, None, rc=c0, **kw)
-        part.assemble(c0)
-        b_schur = rc - c0
-        count = [0]
-        if self._schur is None:
-            self._schur = _StripSchur(self, vs, graph=self._velocity_graph)
-
-        def schur_mv(dp):
-            count[0] += 1
-            return self._schur(dp)
-
-        pin = self._pin_local
-
-        def precon(c):
-            z = c / self._Mdiag
-            if pin >= 0:
-                z[pin] = c[pin]
-            return z
-
-        it = [0]
-        prog = getattr(self, "_progress", 0)
-        t_start = time.perf_counter()
-
-        def cb(est):
-            it[0] += 1
-            if 'LGMRES_iter' in self._iprint or (prog and it[0] % prog == 0):
-                print(f'NavierStokes GMRES: {it[0]}\t{est}\t{time.perf_counter() - t_start:.1f}s', flush=True)
-
-        # restart and maxiter from sizes every rank shares (the largest strip, the global N): the ranks
-        # run the same Arnoldi iterations and so call the same collectives
-        restart = max(1, min(self.N, self._max_basis, int(32e9 // (16 * part.max_local_dofs()))))
-        r = gmres(schur_mv, b_schur, x0=self._dev(dp0), atol=self._mtol * np.sqrt(self.N), rtol=0.0,
-                  restart=restart, maxiter=10 * self.N, precond=precon, callback=cb, inner=part.inner)
-        if r.info != 0:
-            raise RuntimeError(f'NavierStokes LGMRES: Failed to converge in {r.info} iterations')
-        dp = r.x
-        self.schur_matvecs = count[0] - r.discarded     # a dropped speculative matvec is not counted (ADVICE r4)
-        self.schur_discarded = r.discarded
-        b_u, b_v = torch.empty_like(dp), torch.empty_like(dp)
-        m.ns_apply(None, None, dp, b_u, b_v, **kw)
-        part.assemble(b_u, b_v)
-        du, dv = vs.solve(ru - b_u, rv - b_v)
-        return self._out(du, dres_u), self._out(dv, dres_u), self._out(dp, dres_u)
+        return self._schur_update(self._forward_variant(), (dres_u, dres_v, dres_cont), dp0)
 
     def _velocity_solver(self):
         """Device factorisation of the Dirichlet-row-replaced velocity Jacobian -- the reference's
@@ -482,13 +398,6 @@ class NavierStokesSolver:
         self._part.assemble(ru, rv)
         return torch.stack((ru.view(-1, NY), rv.view(-1, NY)), dim=1).reshape(-1, 2 * NY)
 
-    def _whole_mesh_only(self, what, adjoint=False):
-        """Refuse `what` on a partitioned solver; adjoint=True: unless partition_adjoint opted in."""
-        if self._part is not None and not (adjoint and self._partition_adjoint):
-            raise ValueError(f"NavierStokes: {what} is implemented for whole-mesh solvers only " +
-                             ("unless the partitioned solver was built with partition_adjoint=True" if adjoint else
-                              "(no transposed strip solve)"))
-
     def _velocity_apply_lines_T(self, X):
         """J_D^T X for the velocity Jacobian of this linearisation on (NX, 2 NY) line arrays (the transpose of
         _velocity_apply_lines' operator): with z' = (1 - m) z (m the Dirichlet mask),
@@ -500,10 +409,9 @@ class NavierStokesSolver:
         m, NY = self._mesh, self._mesh.NY
         kw = self._jac_kw
         sys = {k: kw[k] for k in ("c_stiff", "c_mass", "c_gradx", "cu", "c_grady", "cv")}
-        if getattr(self, "_free", None) is None:   # 1 - m on the device
-            self._free = m.to_device((~self._dir.mask_np).astype(np.float64))
+        free = self._free_rows()
         zu, zv = X[:, :NY].reshape(-1).contiguous(), X[:, NY:].reshape(-1).contiguous()
-        yu, yv = kw["jvu"] * (self._free * zv), kw["juv"] * (self._free * zu)
+        yu, yv = kw["jvu"] * (free * zv), kw["juv"] * (free * zu)
         m.apply_transpose(zu, yu, diag=kw["juu"], c_acc=1.0, dir_mode=_lib.DIR_IDENTITY, **sys, **self._dir.kw())
         m.apply_transpose(zv, yv, diag=kw["jvv"], c_acc=1.0, dir_mode=_lib.DIR_IDENTITY, **sys, **self._dir.kw())
         return torch.stack((yu.view(-1, NY), yv.view(-1, NY)), dim=1).reshape(-1, 2 * NY)
@@ -558,11 +466,120 @@ class NavierStokesSolver:
 
     def _mass_precond(self, c):
         """The reference's Schur preconditioner (NavierStokes_Solver.py:207-212): the inverse mass diagonal, the
-        identity on the pinned row.  Diagonal, so it preconditions S and S^T alike."""
+        identity on the pinned row (when this rank holds it).  Diagonal, so it preconditions S and S^T alike."""
         z = c / self._Mdiag
-        if self._pin >= 0:
-            z[self._pin] = c[self._pin]
+        if self._pin_local >= 0:
+            z[self._pin_local] = c[self._pin_local]
         return z
+
+    def _restart(self, size):
+        """The basis and its preconditioned images (2 restart N doubles = 16 N bytes per vector) within 32 GB:
+        unrestarted up to max_basis on cfg3/cfg4, restarted at 846 vectors on a whole-mesh cfg5 solver (N = 1537^2 =
+        2.36 M; 31.9 GB).  The velocity factor, the Schur graph's buffers and the Hessenberg matrix come on top of
+        this budget.  Twice that (V only, as krylov.gmres keeps no M^-1 V for the linear mass-diagonal
+        preconditioner) measured no faster at cfg5 -- fewer iterations in the long first solves, each dearer
+        (profiles/r04/cfg5/cfg5_restart1694.json).  On the strips `size` is the largest strip and N the global
+        count, sizes every rank shares: the ranks run the same Arnoldi iterations and so call the same collectives."""
+        return max(1, min(self.N, self._max_basis, int(32e9 // (16 * size))))
+
+    def _recycle(self, restart):
+        if self._recycle_bytes and self._schur_recycle is None:
+            cap = min(self.N, max(restart + 1, int(self._recycle_bytes // (16 * self.N))))
+            self._schur_recycle = Recycle(self.N, torch.float64, self._mesh.device, cap)
+        return self._schur_recycle
+
+    def _forward_variant(self):
+        """_schur_update's record for _get_update: on the whole mesh GCRO (recycling when asked for) over the
+        captured _SchurComplement under either preconditioner; on the strips the GMRES with all-reduced inner
+        products over _StripSchur, every launch followed by the interface assembly."""
+        m, part, kw = self._mesh, self._part, self._ns_kw(pin_first=False)
+        assemble = part.assemble if part is not None else (lambda *ys: None)
+
+        def pressure_rhs(fu, fv, c0):    # dres_cont(J^-1 [ru; rv], 0)
+            m.ns_apply(fu, fv, None, rc=c0, **kw)
+            assemble(c0)
+
+        def velocity_rhs(dp, ru, rv):
+            b_u, b_v = torch.empty_like(dp), torch.empty_like(dp)
+            m.ns_apply(None, None, dp, b_u, b_v, **kw)
+            assemble(b_u, b_v)
+            return ru - b_u, rv - b_v
+
+        if part is not None:
+            vs = self._strip_velocity_solver()
+            return _SchurVariant("GMRES", "LGMRES", vs.solve, pressure_rhs, velocity_rhs, "_schur",
+                                 lambda: _StripSchur(self, vs, graph=self._velocity_graph), self._mass_precond,
+                                 part.max_local_dofs(), gmres,
+                                 lambda restart: dict(maxiter=10 * self.N, inner=part.inner),
+                                 progress=True, clock=True, report=False)
+        vs = self._velocity_solver()
+        return _SchurVariant("GMRES", "LGMRES", vs.solve, pressure_rhs, velocity_rhs, "_schur",
+                             lambda: _SchurComplement(self, vs, graph=self._velocity_graph),
+                             self._pcd if self._schur_precond == "pcd" else self._mass_precond, self.N, gcro,
+                             lambda restart: dict(maxiter=self._schur_maxiter, recycle=self._recycle(restart)),
+                             progress=True, clock=False, report=True)
+
+    def _adjoint_variant(self):
+        """_schur_update's record for _get_update_T on the whole mesh: the transposed solves and launches, plain
+        GMRES over _SchurComplementT, no recycling."""
+        m, kw = self._mesh, self._ns_kw(pin_first=False)
+        vs = self._velocity_solver_T()
+
+        def pressure_rhs(fu, fv, c0):    # B^T f
+            m.ns_apply_transpose(fu, fv, None, yp=c0, **kw)
+
+        def velocity_rhs(q, bu, bv):     # [bu; bv] - C^T q
+            gu, gv = torch.empty_like(q), torch.empty_like(q)
+            m.ns_apply_transpose(None, None, q, gu, gv, c_div=-1.0, **kw)
+            return bu + gu, bv + gv
+
+        return _SchurVariant("adjoint GMRES", "adjoint GMRES", vs.solve_T, pressure_rhs, velocity_rhs, "_schur_T",
+                             lambda: _SchurComplementT(self, vs, graph=self._velocity_graph), self._mass_precond,
+                             self.N, gmres, lambda restart: dict(maxiter=self._schur_maxiter),
+                             progress=False, clock=False, report=True)
+
+    def _schur_update(self, var, rhs, x0):
+        """The block elimination of _get_update and _get_update_T, once: with the variant's velocity solve J^-1 (or
+        J^-T), launches and Schur operator S (or S^T),
+            f = J^-1 [ru; rv],   S dp = rc - (pressure rows of f),   [du; dv] = J^-1 (velocity_rhs(dp, ru, rv)),
+        the Schur system by the variant's Krylov function under its right preconditioner with the reference's
+        stopping rule ||r||_2 <= mtol sqrt(N) (NavierStokes_Solver.py:222-224).  The Schur operator is built on
+        first use and kept in the variant's slot until _calc_jacobians runs again."""
+        ru, rv, rc = (self._dev(a) for a in rhs)
+        fu, fv = var.solve(ru, rv)
+        c0 = torch.empty_like(rc)
+        var.pressure_rhs(fu, fv, c0)
+        b_schur = rc - c0
+        if getattr(self, var.slot) is None:
+            setattr(self, var.slot, var.operator())
+        count, it = [0], [0]
+
+        def schur_mv(dp):
+            count[0] += 1
+            return getattr(self, var.slot)(dp)
+
+        prog = self._progress if var.progress else 0
+        t_start = time.perf_counter()
+
+        def cb(est):
+            it[0] += 1
+            if 'LGMRES_iter' in self._iprint or (prog and it[0] % prog == 0):
+                took = f'\t{time.perf_counter() - t_start:.1f}s' if var.clock else ''
+                print(f'NavierStokes {var.name}: {it[0]}\t{est}{took}', flush=True)
+
+        restart = self._restart(var.size)
+        r = var.krylov(schur_mv, b_schur, x0=self._dev(x0), atol=self._mtol * np.sqrt(self.N), rtol=0.0,
+                       restart=restart, precond=var.precond, callback=cb, **var.kw(restart))
+        if r.info != 0:
+            raise RuntimeError(f'NavierStokes {var.fail}: Failed to converge in {r.info} iterations')
+        dp = r.x
+        self.schur_matvecs = count[0] - r.discarded     # a dropped speculative matvec is not counted (ADVICE r4)
+        self.schur_discarded = r.discarded
+        if var.report and 'LGMRES_suc' in self._iprint:
+            res = (schur_mv(dp) - b_schur).abs().max().item()
+            print(f'NavierStokes {var.name}: Converged in {self.schur_matvecs} evaluations with max-norm {res}')
+        du, dv = var.solve(*var.velocity_rhs(dp, ru, rv))
+        return self._out(du, rhs[0]), self._out(dv, rhs[0]), self._out(dp, rhs[0])
 
     def _get_update(self, dres_u, dres_v, dres_cont, du0=None, dv0=None, dp0=None):
         """Velocity solve + pressure Schur-complement Krylov solve (NavierStokes_Solver.py:162-236), on
@@ -573,79 +590,9 @@ class NavierStokesSolver:
         unrestarted GMRES with outer augmentation.  A plain GMRES restarted at 0.3 N stagnates on small
         meshes (the Schur complement carries the spurious pressure modes of the equal-order
         discretisation), so the device GMRES runs unrestarted up to max_basis vectors."""
-        if self._part is not None:
-            if self._partition_update == "central":
-                return self._get_update_partitioned(dres_u, dres_v, dres_cont, du0, dv0, dp0)
-            return self._get_update_strips(dres_u, dres_v, dres_cont, du0, dv0, dp0)
-        vs = self._velocity_solver()
-        m = self._mesh
-        ru, rv, rc = self._dev(dres_u), self._dev(dres_v), self._dev(dres_cont)
-        fu, fv = vs.solve(ru, rv)
-        c0 = torch.empty_like(rc)
-        m.ns_apply(fu, fv, None, rc=c0, **self._ns_kw(pin_first=False))   # dres_cont(J^-1 [ru; rv], 0)
-        b_schur = rc - c0
-        if self._schur is None:
-            self._schur = _SchurComplement(self, vs, graph=self._velocity_graph)
-        count = [0]
-
-        def schur_mv(dp):
-            count[0] += 1
-            return self._schur(dp)
-
-        precon = self._pcd if self._schur_precond == "pcd" else self._mass_precond
-
-        it = [0]
-
-        prog = getattr(self, "_progress", 0)
-
-        def cb(est):
-            it[0] += 1
-            if 'LGMRES_iter' in self._iprint or (prog and it[0] % prog == 0):
-                print(f'NavierStokes GMRES: {it[0]}\t{est}', flush=True)
-
-        # the basis and its preconditioned images (2 restart N doubles = 16 N bytes per vector) within
-        # 32 GB: unrestarted up to max_basis on cfg3/cfg4, restarted at 846 vectors on a whole-mesh cfg5
-        # solver (N = 1537^2 = 2.36 M; 31.9 GB).  The velocity factor, the Schur graph's buffers and
-        # the Hessenberg matrix come on top of this budget.
-        # restart within 16 bytes per DOF per vector (847 at cfg5): twice that (V only, as krylov.gmres keeps no
-        # M^-1 V for the linear mass-diagonal preconditioner) measured no faster at cfg5 -- fewer iterations in the
-        # long first solves, each dearer (profiles/r04/cfg5/cfg5_restart1694.json)
-        restart = max(1, min(self.N, self._max_basis, int(32e9 // (16 * self.N))))
-        if self._recycle_bytes and self._schur_recycle is None:
-            cap = min(self.N, max(restart + 1, int(self._recycle_bytes // (16 * self.N))))
-            self._schur_recycle = Recycle(self.N, torch.float64, self._mesh.device, cap)
-        r = gcro(schur_mv, b_schur, x0=self._dev(dp0), atol=self._mtol * np.sqrt(self.N), rtol=0.0,
-                 restart=restart, maxiter=self._schur_maxiter, precond=precon, callback=cb,
-                 recycle=self._schur_recycle)
-        if r.info != 0:
-            raise RuntimeError(f'NavierStokes LGMRES: Failed to converge in {r.info} iterations')
-        dp = r.x
-        self.schur_matvecs = count[0] - getattr(r, "discarded", 0)   # dropped speculations are not counted
-        self.schur_discarded = getattr(r, "discarded", 0)
-        if 'LGMRES_suc' in self._iprint:
-            res = (schur_mv(dp) - b_schur).abs().max().item()
-            print(f'NavierStokes GMRES: Converged in {self.schur_matvecs} evaluations with max-norm {res}')
-        b_u, b_v = torch.empty_like(dp), torch.empty_like(dp)
-        m.ns_apply(None, None, dp, b_u, b_v, **self._ns_kw(pin_first=False))
-        du, dv = vs.solve(ru - b_u, rv - b_v)
-        return self._out(du, dres_u), self._out(dv, dres_u), self._out(dp, dres_u)
-
-    def _operator(self, x, c_mass=0.0, c_stiff=0.0, cu=None, cv=None, free=False):
-        """(c_mass M + c_stiff K + diag(cu) G_x + diag(cv) G_y) x on this solver's mesh in one fused launch, no
-        row replaced; free=True zeroes the velocity Dirichlet rows.  What the coupler's parameter partials and the
-        functionals (solvers/functionals.py) are built from.  NumPy in, NumPy out; device tensors likewise."""
-        self._whole_mesh_only("_operator")
-        kw = {}
-        if cu is not None:
-            kw.update(c_gradx=1.0, cu=self._dev(cu))
-        if cv is not None:
-            kw.update(c_grady=1.0, cv=self._dev(cv))
-        y = self._mesh.apply(self._dev(x), c_mass=c_mass, c_stiff=c_stiff, **kw)
-        if free:
-            if getattr(self, "_free", None) is None:   # 1 - m on the device
-                self._free = self._mesh.to_device((~self._dir.mask_np).astype(np.float64))
-            y = self._free * y
-        return self._out(y, x)
+        if self._part is not None and self._partition_update == "central":
+            return self._get_update_partitioned(dres_u, dres_v, dres_cont, du0, dv0, dp0)
+        return self._schur_update(self._forward_variant(), (dres_u, dres_v, dres_cont), dp0)
 
     # ------------------------------------------------------------------ reverse mode
     def _get_dresiduals_T(self, ru_bar, rv_bar, rc_bar, want_T=False):
@@ -690,90 +637,7 @@ class NavierStokesSolver:
                              "would need a transposed line condensation")
         if self._jac_kw is None:
             raise RuntimeError("NavierStokes: _get_residuals and _calc_jacobians must run before _get_update_T")
-        vs = self._velocity_solver_T()
-        m = self._mesh
-        kw = self._ns_kw(pin_first=False)
-        bu, bv, bp = self._dev(du_bar), self._dev(dv_bar), self._dev(dp_bar)
-        fu, fv = vs.solve_T(bu, bv)
-        c0 = torch.empty_like(bp)
-        m.ns_apply_transpose(fu, fv, None, yp=c0, **kw)    # B^T f
-        b_schur = bp - c0
-        if self._schur_T is None:
-            self._schur_T = _SchurComplementT(self, vs, graph=self._velocity_graph)
-        count = [0]
-
-        def schur_mv(q):
-            count[0] += 1
-            return self._schur_T(q)
-
-        it = [0]
-
-        def cb(est):
-            it[0] += 1
-            if 'LGMRES_iter' in self._iprint:
-                print(f'NavierStokes adjoint GMRES: {it[0]}\t{est}', flush=True)
-
-        restart = max(1, min(self.N, self._max_basis, int(32e9 // (16 * self.N))))   # _get_update's rule
-        r = gmres(schur_mv, b_schur, x0=self._dev(dres_c0), atol=self._mtol * np.sqrt(self.N), rtol=0.0,
-                  restart=restart, maxiter=self._schur_maxiter, precond=self._mass_precond, callback=cb)
-        if r.info != 0:
-            raise RuntimeError(f'NavierStokes adjoint GMRES: Failed to converge in {r.info} iterations')
-        q = r.x
-        self.schur_matvecs = count[0] - r.discarded     # dropped speculations are not counted
-        self.schur_discarded = r.discarded
-        if 'LGMRES_suc' in self._iprint:
-            res = (schur_mv(q) - b_schur).abs().max().item()
-            print(f'NavierStokes adjoint GMRES: Converged in {self.schur_matvecs} evaluations with max-norm {res}')
-        gu, gv = torch.empty_like(q), torch.empty_like(q)
-        m.ns_apply_transpose(None, None, q, gu, gv, c_div=-1.0, **kw)    # -C^T q
-        lu, lv = vs.solve_T(bu + gu, bv + gv)
-        return self._out(lu, du_bar), self._out(lv, du_bar), self._out(q, du_bar)
-
-    def _get_update_T_partitioned(self, du_bar, dv_bar, dp_bar, dres_c0):
-        """_get_update_T of a strip-partitioned solver, run centrally whatever partition_update says (the mirror of
-        _get_update_partitioned): the linearisation and the three right-hand sides are gathered, rank 0's whole-mesh
-        counterpart (the same cached twin) takes the linearisation through _get_residuals / _calc_jacobians when it
-        is stale and runs _get_update_T, and the result is broadcast; a failure on rank 0 travels as a NaN status so
-        that every rank raises.  This is the functional path, not the scalable one: every call moves whole-mesh
-        vectors through rank 0.  A distributed adjoint Schur solve S^T q = E^T q - B^T J^-T C^T q needs the
-        transposed strip solvers, which do not exist yet."""
-        part = self._part
-        lin = self._lin
-        if lin is None:
-            raise RuntimeError("NavierStokes: _get_residuals and _calc_jacobians must run before _get_update_T")
-        stale = lin.get("stale")
-        if stale:
-            us, vs = (self._global(a) for a in lin["sys"])
-            uj, vj = (self._global(a) for a in lin["jac"])
-            lin["stale"] = False
-        rhs = [self._global(a) for a in (du_bar, dv_bar, dp_bar)]
-        q0 = None if dres_c0 is None else self._global(dres_c0)
-        out = torch.zeros(3 * self.N + 1, dtype=torch.float64)
-        err = None
-        if part.rank == 0:
-            try:
-                if stale:
-                    if self._twin is None:
-                        self._twin = self._central_solver()
-                    z = np.zeros(self.N)
-                    self._twin._get_residuals(us, vs, z, z)
-                    self._twin._calc_jacobians(uj, vj)
-                lam = self._twin._get_update_T(*rhs, dres_c0=q0)
-                out[:3 * self.N] = torch.from_numpy(np.concatenate([np.asarray(a) for a in lam]))
-                out[-1] = float(getattr(self._twin, "schur_matvecs", -1))
-            except (RuntimeError, ValueError) as e:
-                err = e
-                out[-1] = float("nan")
-        out = part.broadcast(out)
-        if err is not None:
-            raise err
-        if torch.isnan(out[-1]):
-            raise RuntimeError("NavierStokes: the adjoint update failed on rank 0 (see its error)")
-        self.schur_matvecs = int(out[-1].item())
-        lam = [out[i * self.N:(i + 1) * self.N].cpu().numpy() for i in range(3)]
-        if isinstance(du_bar, torch.Tensor):
-            return tuple(self._dev(a) for a in lam)
-        return tuple(lam)
+        return self._schur_update(self._adjoint_variant(), (du_bar, dv_bar, dp_bar), dres_c0)
 
     def _get_solution(self, T, u0=None, v0=None, p0=None):
         """Newton iteration (NavierStokes_Solver.py:238-270), iterates kept on the device; NumPy in,
@@ -805,13 +669,6 @@ class NavierStokesSolver:
             p = p + dp
             self._k += 1
         return self._out(u, like), self._out(v, like), self._out(p, like)
-
-    def _get_vector(self, f_func):
-        return f_func(self.points[0], self.points[1])
-
-    def _get_interpol(self, f, points_plot):
-        f_e = SEM.scatter(f, self._P, self._N_ex, self._N_ey)
-        return SEM.eval_interpolation(f_e, self.points_e, points_plot)
 
     def run(self, T_func, points_plot):
         T = self._get_vector(T_func)

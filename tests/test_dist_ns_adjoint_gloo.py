@@ -244,6 +244,54 @@ def _fail_worker(rank, world, port, q):
         dist.destroy_process_group()
 
 
+def _stale_worker(rank, world, port, q):
+    """A forward and an adjoint central update on one linearisation, then an adjoint update on the next: how often
+    the whole-mesh counterpart is handed the linearisation."""
+    _setup(rank, world, port)
+    try:
+        from cpu_mesh_nsT import CPUStripMeshNST
+        from sem_amd.parallel import Partition
+        from sem_amd.solvers import NavierStokesSolver
+        P, nex, ney = 4, 3, 3
+        calls = {"residuals": 0, "jacobians": 0}
+
+        class Counting(_twin_class()):
+            def _get_residuals(self, *a):
+                calls["residuals"] += 1
+                return super()._get_residuals(*a)
+
+            def _calc_jacobians(self, *a):
+                calls["jacobians"] += 1
+                return super()._calc_jacobians(*a)
+
+        ns = NavierStokesSolver(1.0, 1.0, 60.0, 0.0, P, nex, ney, u_N=1.0, mtol=1e-9, iprint=[],
+                                partition=Partition(dist, mesh_factory=CPUStripMeshNST), partition_update="central",
+                                partition_adjoint=True)
+        twin = Counting(1.0, 1.0, 60.0, 0.0, P, nex, ney, mtol=1e-9)
+        ns._central_solver = lambda: twin
+        r = np.random.default_rng(5)
+        u, v, p, T = (0.1 * r.uniform(-1, 1, ns.N) for _ in range(4))
+        b = [r.uniform(-1, 1, ns.N) for _ in range(3)]
+        ns._get_residuals(u, v, p, T)
+        ns._calc_jacobians(u, v)
+        ns._get_update(*b)
+        ns._get_update_T(*b)
+        first = dict(calls)
+        ns._calc_jacobians(v, u)
+        ns._get_update_T(*b)
+        q.put((rank, (first, dict(calls))))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_forward_and_adjoint_central_updates_share_one_refresh():
+    """_get_update then _get_update_T on one linearisation hand it to rank 0's counterpart once (one staleness record
+    for both); the next _calc_jacobians makes it stale again.  The other rank never touches its counterpart."""
+    res = _run(_stale_worker, 2, ())
+    assert res[0] == ({"residuals": 1, "jacobians": 1}, {"residuals": 2, "jacobians": 2})
+    assert res[1] == ({"residuals": 0, "jacobians": 0}, {"residuals": 0, "jacobians": 0})
+
+
 def test_rank0_adjoint_update_failure_reaches_every_rank():
     res = _run(_fail_worker, 2, (), limit=120)
     assert "Failed to converge" in res[0]

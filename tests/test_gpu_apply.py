@@ -330,6 +330,26 @@ def test_bad_arguments_raise(gpu):
         mesh.apply(x.float(), c_stiff=1.0)
 
 
+def test_dir_mask_off_the_mesh_device_is_refused(gpu):
+    """Every entry point that takes an explicit Dirichlet mask refuses one that is not on the mesh's device (its
+    pointer would be handed to a kernel that cannot read it), before anything is launched."""
+    from sem_amd.device import get_mesh
+    mesh = get_mesh(2, 2, 2, 0.5, 0.5)
+    x = torch.zeros(mesh.n_local, dtype=torch.float64, device=mesh.device)
+    host = torch.zeros(mesh.n_local, dtype=torch.uint8)
+    calls = (lambda m: mesh.apply(x, dir_mask=m), lambda m: mesh.apply_transpose(x, dir_mask=m),
+             lambda m: mesh.apply_transpose_part(x, dir_mask=m),
+             lambda m: mesh.ns_apply(x, x, x, x.clone(), dir_mask=m),
+             lambda m: mesh.ns_apply_transpose(x, x, x, x.clone(), dir_mask=m),
+             lambda m: mesh.ns_apply_transpose_part(x, x, x, x.clone(), dir_mask=m),
+             lambda m: mesh.velocity_blocks({}, dir_mask=m), lambda m: mesh.condensed_blocks({}, dir_mask=m))
+    for call in calls:
+        with pytest.raises(ValueError, match="dir_mask must be a uint8 tensor of n_local entries"):
+            call(host)
+        with pytest.raises(ValueError, match="dir_mask must be a uint8 tensor of n_local entries"):
+            call(host.to(mesh.device)[:-1])
+
+
 def test_kernel_names(gpu, tuning):
     """sem_kernel_name reports the kernel sem_apply selects (sem_amd/csrc/apply_select.h): tile shapes per order,
     the knobs' variants, and the DPP coefficient mode from 2^20 local nodes up (the two P = 8 meshes straddle it).
