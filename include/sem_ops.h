@@ -483,6 +483,27 @@ int sem_gemv_rows(int M, int K, double alpha, const double* A, int64_t lda, cons
  * is ~N_ex + 1 dependent launches instead of 2 N_ex (velocity_solve.py twisted_thomas_solve). */
 int sem_gemv_rows2(int M, double alpha, double beta, int K0, const double* A0, int64_t lda0, const double* x0,
                    double* y0, int K1, const double* A1, int64_t lda1, const double* x1, double* y1, void* stream);
+/* The transposed twins (entry points added at ABI 15; sem_amd/csrc/block_gemv.hip row_gemv_t_kernel):
+ *   y[c] = alpha sum_{r<M} A[r lda + c] x[r] + beta y[c]      c < K
+ * for the same row-major M x K operators (lda >= K; x: M entries, y: K entries; beta = 0: y is not read) -- one step
+ * of the transposed block-Thomas sweeps (velocity_solve.py *_thomas_solve_T), the strip solve's X01^T g and its
+ * transposed reduced rows Z^T h (strip_solve.py).  Lanes run along the contiguous columns, the rows are split over
+ * the row groups of one workgroup, x is staged in LDS a chunk at a time (M is not bounded); no workgroup talks to
+ * another (no atomics).  form: 1 = wide (64 columns per workgroup), 2 = narrow (16 columns: a short-K operator still
+ * spreads over the chip), 0 = by size (wide where the wide workgroups number at least 256).  8-byte loads work for any
+ * alignment and any parity of K and lda; 16-byte loads are used when A and y are 16-byte aligned and K and lda are
+ * even.  Every column's products are summed in one order whatever the form and the load width (32 row slices, eight
+ * interleaved sums per slice): results are bitwise equal across them and bitwise repeatable.
+ * sem_gemv_rows2_t: two independent products with a common M and their own K_j, lda_j in ONE launch (the two chains
+ * of the twisted sweep); a product with K_j = 0 is skipped.
+ * Device pointers; y must not overlap A or x, and y0 must not overlap y1.  Stream-ordered, nothing allocated.
+ * SEM_EINVAL for negative sizes, lda < K, form outside 0..2 or null pointers, before any launch.  K = 0: SEM_OK, no
+ * launch.  M = 0: y = 0 is written when beta = 0; otherwise SEM_OK with no launch (y is left as it is). */
+int sem_gemv_rows_t(int M, int K, double alpha, const double* A, int64_t lda, const double* x, double beta, double* y,
+                    int form, void* stream);
+int sem_gemv_rows2_t(int M, double alpha, double beta, int K0, const double* A0, int64_t lda0, const double* x0,
+                     double* y0, int K1, const double* A1, int64_t lda1, const double* x1, double* y1, int form,
+                     void* stream);
 
 /* ---- nested-dissection solve of the velocity Jacobian (ABI 14) ---------- */
 /* The streaming steps of sem_amd/solvers/nested_dissection.py, which orders the Dirichlet-row-replaced velocity
@@ -553,8 +574,9 @@ int sem_leaf_forward(const sem_leaf_launch* d, void* stream);
 /* The steps of NestedDissectionSolver.solve_T: the same stored operators as the forward solve, streamed the other
  * way (no transposed copies).  What exists: the velocity factor's transposed solve, and the
  * transposed line condensation (sem_nested_solve_t, sem_block_gemv_t above: the nested interior on the block-Thomas
- * edge form and the cyclic-reduction sweep).  What does not: a transposed Schur solve, strips, transposed twins of
- * the ABI-11 coupled forms, HIP for the transposed block-Thomas interface sweeps and the dense edge inverse.
+ * edge form, the cyclic-reduction sweep, and the block-Thomas sweeps on sem_gemv_rows_t above, which also carry the
+ * strip line solve's transposed interface step).  What does not: a transposed Schur solve, the nested-dissection strip
+ * solve, transposed twins of the ABI-11 coupled forms and the dense edge inverse.
  * sem_front_gemv_t: one launch = one level of y_f = A_f^T x_f.  Item f has a ROW-MAJOR operator at op[f] (device
  * address, 16-byte aligned; dims[4 f .. 4 f + 2] = R_f operand rows, K_f output columns, leading dimension ld_f;
  * K_f and ld_f even, K_f <= ld_f), its R_f operand positions in W at xidx[xoff[f] ..] (-1: a zero operand) and

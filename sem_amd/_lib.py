@@ -168,6 +168,11 @@ _SIGS = {
     "sem_leaf_transpose": (C.c_int, [C.POINTER(SemLeafTLaunch), C.c_void_p]),
     "sem_gemv_rows": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_double,
                                 C.c_void_p, C.c_void_p]),
+    "sem_gemv_rows_t": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_double,
+                                  C.c_void_p, C.c_int, C.c_void_p]),
+    "sem_gemv_rows2_t": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                   C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_void_p]),
 }
 
 _lib = None

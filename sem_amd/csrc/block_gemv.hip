@@ -336,9 +336,172 @@ static void launch_row_gemv(RowGemv2Args& g, int M, int parts, bool vec, hipStre
   launch_row_gemv_ru<2, 8>(g, M, parts, s);
 }
 
+// ---- Streaming transposed GEMV: y = alpha A^T x + beta y for the same row-major M x K operators, read once per
+// call -- the steps of the TRANSPOSED block-Thomas sweeps (velocity_solve.py *_thomas_solve_T: F^T z, Uh^T z), the
+// strip solve's X01^T g_int and its transposed reduced rows Z^T h (strip_solve.py).  The shape is
+// block_gemv_t_kernel's, not the forward row kernel's: lanes run along the contiguous columns, the M rows are split
+// over the row groups of one 256-thread workgroup, every lane keeps kRowTUnroll independent sums per column (that
+// many row loads in flight), x is staged in LDS kRowTStage doubles at a time (M is not bounded: X01 has ~21,000 rows
+// at cfg5), and the sums meet in LDS.  No workgroup talks to another: no atomics, no split of the rows across
+// workgroups.
+// A workgroup takes COLS columns: 64 (wide form, 512-byte row segments) or 16 (narrow form, 128-byte segments, so a
+// short-K operator still spreads over the chip: K = 2m = 6,148 at cfg5 is 385 narrow workgroups against 97 wide).
+// VEC: 16-byte loads, two columns per lane (COLS / 2 lanes per row group); otherwise 8-byte loads, one column per
+// lane, for any alignment and parity of K and lda (F[:, m:] with odd m, views that start one double into a row).
+// Summation order of a column, the same for every (COLS, VEC): the rows are cut into kRowTSlices = 32 slices
+// [M s / 32, M (s + 1) / 32); row r of slice s goes to sum (r - start_s) % 8 of that slice, in increasing r; a
+// slice's eight sums combine as ((0+1)+(2+3))+((4+5)+(6+7)); the slices' sums are added in slice order.  A row group
+// owns 32 / groups consecutive slices (8, 4, 2 or 1) and walks them one after the other, so the four kernels differ
+// only in which thread holds a sum: results are bitwise equal across both load widths and both forms, and bitwise
+// repeatable.
+// By-size rule of form 0 (sem_gemv_rows_t): the wide form where its 64-column workgroups number at least 256 (one
+// per CU), the narrow form below that.  Measured at the cfg5 shapes, m = 3,074, operators cycled out of the MALL
+// (tools/strip_solve_T_probe.py, profiles/strip_solve_T/gemv_rows_t_rates.json; TB/s wide | narrow | torch A.mT @ x |
+// sem_gemv_rows on the same operator):  m x m 1.60 | 2.43 | 0.43 | 4.64;  m x 2m 3.08 | 3.09 | 0.87 | 5.38;
+// X01 7m x 2m 3.44 | 3.56 | 0.92 | 6.17;  Z 2m x 9m (433 wide workgroups) 5.70 | 3.70 | 3.55 | 6.08.  The short-K
+// operators are latency-bound (the m x m product is 31 us): each of their few workgroups walks all M rows.
+constexpr int kRowTSlices = 32;
+constexpr int kRowTUnroll = 8;
+constexpr int kRowTStage = 2048;  // doubles of x in LDS per workgroup and step (16 KB), shared out over the row groups
+
+template <int COLS, bool VEC>
+__global__ __launch_bounds__(256) void row_gemv_t_kernel(const RowGemv2Args g) {
+  constexpr int W = VEC ? 2 : 1, LANES = COLS / W, G = 256 / LANES, SPG = kRowTSlices / G, CH = kRowTStage / G;
+  constexpr int U = kRowTUnroll;
+  static_assert(SPG >= 1 && SPG * G == kRowTSlices && CH % U == 0 && U == 8, "row_gemv_t_kernel: slice layout");
+  __shared__ double xs[G][CH];
+  __shared__ double part[kRowTSlices][COLS];
+  const bool second = static_cast<int>(blockIdx.x) >= g.nb0;
+  const RowGemvArgs a = second ? g.p[1] : g.p[0];
+  const int tile = static_cast<int>(blockIdx.x) - (second ? g.nb0 : 0);
+  const int lane = threadIdx.x % LANES, grp = threadIdx.x / LANES;
+  const int c = tile * COLS + lane * W;
+  const double* Ac = a.A + min(c, a.K - W);  // clamped columns are computed, not stored (VEC: K is even)
+  const int M = a.M;
+  const int nch = ((M + kRowTSlices - 1) / kRowTSlices + CH - 1) / CH;  // chunks of the longest slice: uniform
+  const double* xr = xs[grp];
+  for (int i = 0; i < SPG; ++i) {
+    const int s = grp * SPG + i;
+    const int rb = static_cast<int>(static_cast<int64_t>(M) * s / kRowTSlices);
+    const int re = static_cast<int>(static_cast<int64_t>(M) * (s + 1) / kRowTSlices);
+    double acc[U][W];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int w = 0; w < W; ++w) acc[u][w] = 0.0;
+    for (int t = 0; t < nch; ++t) {
+      // chunk starts are multiples of CH (of U) past the slice start: row r always meets sum (r - rb) % U
+      const int c0 = min(re, rb + t * CH), c1 = min(re, c0 + CH);
+      if (i | t) __syncthreads();  // the group is done with its previous chunk
+      for (int j = lane; c0 + j < c1; j += LANES) xs[grp][j] = a.x[c0 + j];
+      __syncthreads();
+      int r = c0;
+      for (; r + U <= c1; r += U) {
+        if constexpr (VEC) {
+          double2 v[U];
+#pragma unroll
+          for (int u = 0; u < U; ++u) v[u] = load_a2<true>(Ac + static_cast<int64_t>(r + u) * a.lda);
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            const double xv = xr[r - c0 + u];
+            acc[u][0] = fma(v[u].x, xv, acc[u][0]);
+            acc[u][W - 1] = fma(v[u].y, xv, acc[u][W - 1]);
+          }
+        } else {
+          double v[U];
+#pragma unroll
+          for (int u = 0; u < U; ++u) v[u] = __builtin_nontemporal_load(Ac + static_cast<int64_t>(r + u) * a.lda);
+#pragma unroll
+          for (int u = 0; u < U; ++u) acc[u][0] = fma(v[u], xr[r - c0 + u], acc[u][0]);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U - 1; ++u)  // the slice's last rows (c1 == re here)
+        if (r + u < c1) {
+          const double xv = xr[r - c0 + u];
+          if constexpr (VEC) {
+            const double2 v = load_a2<true>(Ac + static_cast<int64_t>(r + u) * a.lda);
+            acc[u][0] = fma(v.x, xv, acc[u][0]);
+            acc[u][W - 1] = fma(v.y, xv, acc[u][W - 1]);
+          } else {
+            acc[u][0] = fma(__builtin_nontemporal_load(Ac + static_cast<int64_t>(r + u) * a.lda), xv, acc[u][0]);
+          }
+        }
+    }
+#pragma unroll
+    for (int w = 0; w < W; ++w)
+      part[s][lane * W + w] = ((acc[0][w] + acc[1][w]) + (acc[2][w] + acc[3][w])) +
+                              ((acc[4][w] + acc[5][w]) + (acc[6][w] + acc[7][w]));
+  }
+  __syncthreads();
+  const int col = tile * COLS + static_cast<int>(threadIdx.x);
+  if (threadIdx.x < COLS && col < a.K) {
+    double sum = part[0][threadIdx.x];
+    for (int s = 1; s < kRowTSlices; ++s) sum += part[s][threadIdx.x];
+    const double v = M ? a.alpha * sum : 0.0;
+    double* yp = a.y + col;
+    *yp = a.beta == 0.0 ? v : fma(a.beta, *yp, v);
+  }
+}
+
+// 16-byte loads need 16-byte aligned A rows (and y, by the interface's rule) and even K and lda
+static bool row_t_vec(const RowGemvArgs& a) {
+  return (reinterpret_cast<uintptr_t>(a.A) % 16) == 0 && (reinterpret_cast<uintptr_t>(a.y) % 16) == 0 &&
+         (a.lda % 2) == 0 && (a.K % 2) == 0;
+}
+
+// parts = 1 (sem_gemv_rows_t) or 2 (sem_gemv_rows2_t: blocks [0, nb0) the first product, the rest the second); a
+// product with K = 0 has no blocks.  false: nothing to launch.
+static bool launch_row_gemv_t(RowGemv2Args& g, int parts, bool vec, int form, hipStream_t s) {
+  const int K0 = g.p[0].K, K1 = parts == 2 ? g.p[1].K : 0;
+  const bool wide = form == 1 || (form == 0 && (K0 + 63) / 64 + (K1 + 63) / 64 >= 256);
+  const int cols = wide ? 64 : 16;
+  g.nb0 = (K0 + cols - 1) / cols;
+  const int nb = g.nb0 + (K1 + cols - 1) / cols;
+  if (nb == 0) return false;
+  if (wide && vec)
+    hipLaunchKernelGGL((row_gemv_t_kernel<64, true>), dim3(nb), dim3(256), 0, s, g);
+  else if (wide)
+    hipLaunchKernelGGL((row_gemv_t_kernel<64, false>), dim3(nb), dim3(256), 0, s, g);
+  else if (vec)
+    hipLaunchKernelGGL((row_gemv_t_kernel<16, true>), dim3(nb), dim3(256), 0, s, g);
+  else
+    hipLaunchKernelGGL((row_gemv_t_kernel<16, false>), dim3(nb), dim3(256), 0, s, g);
+  return true;
+}
+
 }  // namespace sem
 
 extern "C" {
+
+int sem_gemv_rows_t(int M, int K, double alpha, const double* A, int64_t lda, const double* x, double beta, double* y,
+                    int form, void* stream) {
+  if (M < 0 || K < 0 || lda < K || form < 0 || form > 2) return sem::set_error(SEM_EINVAL, "gemv_rows_t: bad sizes");
+  if (K == 0 || (M == 0 && beta != 0.0)) return SEM_OK;  // no output, or no product to add: y stays as it is
+  if (!y || (M > 0 && (!A || !x))) return sem::set_error(SEM_EINVAL, "gemv_rows_t: null argument");
+  sem::RowGemv2Args g{{sem::RowGemvArgs{A, x, y, lda, alpha, beta, M, K}, sem::RowGemvArgs{}}, 0};
+  sem::launch_row_gemv_t(g, 1, M > 0 && sem::row_t_vec(g.p[0]), form, reinterpret_cast<hipStream_t>(stream));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return sem::set_error(SEM_EHIP, std::string("gemv_rows_t launch: ") + hipGetErrorString(e));
+  return SEM_OK;
+}
+
+int sem_gemv_rows2_t(int M, double alpha, double beta, int K0, const double* A0, int64_t lda0, const double* x0,
+                     double* y0, int K1, const double* A1, int64_t lda1, const double* x1, double* y1, int form,
+                     void* stream) {
+  if (M < 0 || K0 < 0 || K1 < 0 || lda0 < K0 || lda1 < K1 || form < 0 || form > 2)
+    return sem::set_error(SEM_EINVAL, "gemv_rows2_t: bad sizes");
+  if ((K0 == 0 && K1 == 0) || (M == 0 && beta != 0.0)) return SEM_OK;
+  if ((K0 > 0 && (!y0 || (M > 0 && (!A0 || !x0)))) || (K1 > 0 && (!y1 || (M > 0 && (!A1 || !x1)))))
+    return sem::set_error(SEM_EINVAL, "gemv_rows2_t: null argument");
+  sem::RowGemv2Args g{{sem::RowGemvArgs{A0, x0, y0, lda0, alpha, beta, M, K0},
+                       sem::RowGemvArgs{A1, x1, y1, lda1, alpha, beta, M, K1}}, 0};
+  const bool vec = M > 0 && (K0 == 0 || sem::row_t_vec(g.p[0])) && (K1 == 0 || sem::row_t_vec(g.p[1]));
+  sem::launch_row_gemv_t(g, 2, vec, form, reinterpret_cast<hipStream_t>(stream));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return sem::set_error(SEM_EHIP, std::string("gemv_rows2_t launch: ") + hipGetErrorString(e));
+  return SEM_OK;
+}
 
 int sem_gemv_rows(int M, int K, double alpha, const double* A, int64_t lda, const double* x, double beta, double* y,
                   void* stream) {

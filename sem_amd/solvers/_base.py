@@ -11,13 +11,18 @@ class SolverBase:
     _name = ""                   # the solver's name in its messages
     _whole_mesh_note = ""        # what _whole_mesh_only adds to a plain refusal
     _partition_adjoint = False   # reverse mode on a partitioned solver is opt-in
+    _partition_adjoint_modes = ()   # the strings a solver takes for partition_adjoint besides a bool
     _progress = 0                # print the Krylov estimate every _progress iterations (set by tools)
 
     def __init__(self, partition, partition_update, partition_adjoint):
         if partition_update not in ("distributed", "central"):
             raise ValueError("partition_update must be 'distributed' or 'central'")
         self._part, self._partition_update = partition, partition_update
-        self._partition_adjoint = bool(partition_adjoint)
+        if isinstance(partition_adjoint, str) and partition_adjoint not in self._partition_adjoint_modes:
+            raise ValueError(f"partition_adjoint must be a bool" +
+                             "".join(f" or '{v}'" for v in self._partition_adjoint_modes))
+        # the value beside its truthiness: a string names how the partitioned adjoint update is preconditioned
+        self._partition_adjoint, self._partition_adjoint_mode = bool(partition_adjoint), partition_adjoint
         self._free = None        # 1 - Dirichlet mask as a device vector (_free_rows)
         # rank 0's whole-mesh counterpart, the local fields of the linearisation it has to be given, and whether it
         # has them yet: one record for the forward and the adjoint update

@@ -86,6 +86,7 @@ class DirichletRows:
 
 class ConvectionDiffusionSolver(SolverBase):
     _name = "ConvectionDiffusion"
+    _partition_adjoint_modes = ("condensed",)
 
     def __init__(self, L_x: float, L_y: float, Pe: float, P: int, N_ex: int, N_ey: int,
                  T_W: float = None, T_E: float = None, T_S: float = None, T_N: float = None,
@@ -105,8 +106,10 @@ class ConvectionDiffusionSolver(SolverBase):
         the condensed direct preconditioner, the update is broadcast.
         partition_adjoint: opt-in to reverse mode on a partitioned solver -- _get_dresiduals_T and
         _get_update_T then run over the strips (parallel.StripApplyT: each rank's transposed strip apply
-        + the interface exchange); the adjoint solve is the UNPRECONDITIONED distributed GMRES (there is no
-        transposed strip condensation).  Off by default: a partitioned solver refuses both methods."""
+        + the interface exchange).  True: the adjoint solve is the UNPRECONDITIONED distributed GMRES; "condensed":
+        it is right-preconditioned by the element-partitioned condensed direct solve applied transposed
+        (StripLineSolver(adjoint=True).solve1_T: the forward update's factor, nothing stored twice).  Any other
+        string raises ValueError.  Off by default: a partitioned solver refuses both methods."""
         if krylov not in ("device", "scipy"):
             raise ValueError("krylov must be 'device' or 'scipy'")
         if partition is not None and krylov != "device":
@@ -227,15 +230,19 @@ class ConvectionDiffusionSolver(SolverBase):
         on the true residual.  precond=None: the unpreconditioned solve.
         On a partitioned solver (partition_adjoint=True) every iteration is a transposed strip apply plus the
         interface exchange, the inner products are all-reduced (partition.inner), the restart comes from the
-        global N and is the same on every rank, and the solve is NOT preconditioned whatever `precond` says:
-        there is no transposed strip condensation (StripLineSolver has no solve1_T)."""
+        global N and is the same on every rank.  partition_adjoint=True leaves that solve unpreconditioned whatever
+        `precond` says; partition_adjoint="condensed" (with precond="condensed", P > 1) right-preconditions it with
+        the strip factor's transposed solve (StripLineSolver.solve1_T: one transposed GEMV and one all-reduce over the
+        strip-boundary lines per application; captured in a graph when the collective runs on the device)."""
         self._whole_mesh_only("_get_update_T", adjoint=True)
         if self._Sys is None:
             raise RuntimeError("ConvectionDiffusion: _get_residuals must run before _get_update_T")
         kw, precond = {}, None
         if self._part is not None:
             kw = dict(inner=self._part.inner)
-        elif self._precond == "condensed":
+        condensed = self._precond == "condensed" and (
+            self._part is None or (self._partition_adjoint_mode == "condensed" and self._P > 1))
+        if condensed:
             vs = self._jacobian_solver()
             if vs.device.type == "cuda" and vs._graph_T is None:
                 vs.capture_T()
@@ -265,7 +272,8 @@ class ConvectionDiffusionSolver(SolverBase):
                 from .strip_solve import StripLineSolver
                 p = self._part
                 vs = StripLineSolver(self._P, self._N_ex, self._N_ey, m.device, p.part.bounds, p.rank, p.dist,
-                                     group=p.group, ncomp=1, gather_device=p.backend_device())
+                                     group=p.group, ncomp=1, gather_device=p.backend_device(),
+                                     adjoint=self._partition_adjoint_mode == "condensed")
             else:
                 # transpose=True: the same factor preconditions the adjoint solve (_get_update_T); nothing of the
                 # forward solve changes, and what the transposed solve adds is built on its first use

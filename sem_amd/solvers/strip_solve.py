@@ -20,6 +20,11 @@ the interface right-hand side (a shared line's b counted by its right owner only
 elimination to the two boundary lines, ONE all-gather of 2 m doubles per rank, the replicated reduced
 solve, local back substitution, interior back substitution.  x comes out on every rank's lines, equal
 on shared lines.
+Solve of J^T x = b (StripLineSolver(adjoint=True); the same contract, the same factor, nothing stored transposed): the
+transposed interior solves and interface right-hand side, h = [g_0; g_n] - X01^T g_int (the transpose of the back
+substitution), the transposed reduced solve -- ONE transposed GEMV over this rank's rows of R^-1 and ONE all-reduce of
+(G + 1) m doubles (_reduced_solve_T) --, then x_int = T^-T (g_int - S_up0^T x_0 on line 1 - S_lon^T x_n on line n - 1)
+by the transposed block-Thomas sweeps, and the transposed interior back substitution.
 
 The reduced system over the strip-boundary lines (step 3 and the solve's all-gather + GEMV) and the agreed graph
 capture live in `_StripReduced`, which the NS velocity solve's default strip solver shares:
@@ -32,8 +37,9 @@ import os
 import torch
 
 from ..tracing import phase
-from .velocity_solve import (VelocityJacobianSolver, _gemv, _gemv2, fused_thomas_operators, fused_thomas_solve,
-                             pivot_inverse, twisted_thomas_operators, twisted_thomas_solve, twisted_thomas_solve_mat)
+from .velocity_solve import (VelocityJacobianSolver, _gemv, _gemv2, _gemv2_t, _gemv_t, fused_thomas_operators,
+                             fused_thomas_solve, fused_thomas_solve_T, pivot_inverse, twisted_thomas_operators,
+                             twisted_thomas_solve, twisted_thomas_solve_T, twisted_thomas_solve_mat)
 
 
 class _StripReduced:
@@ -150,28 +156,63 @@ class _StripReduced:
                 xb2 = self._red._cr_solve(rhs)[self.rank:self.rank + 2].reshape(-1)
         return xb2
 
-    def capture(self):
-        """Graph capture of the solve: only when the reduced system's all-gather runs on the device (RCCL,
-        capturable); under gloo the all-gather goes through the host, so the solve stays eager.
+    def _reduced_solve_T(self, h):
+        """x on this strip's two boundary lines (2m) from R^T x = rhs, rhs_j the sum of the two neighbours' partial
+        right-hand sides of line j; h (2, m): this strip's.  Rank r holds block rows r, r + 1 of R^-1 (_Z), and row i
+        of R^-1 meets H[i, 0] + H[i - 1, 1] once each over the ranks, so the sum over the ranks of Z^T [h_0; h_1] is
+        R^-T rhs on every line: ONE transposed GEMV and ONE all-reduce of (G + 1) m doubles, no second copy of R^-1.
+        Every rank takes its lines r, r + 1 from the same reduced buffer: shared lines are bitwise equal.
+        SEM_STRIP_REDUCED=cr: the all-gather of the forward solve and the replicated transposed CR solve."""
+        m, G = self.m, self.G
+        if self._Z is None:
+            with phase("strip.allreduce_T"):
+                H = torch.stack(self._all_gather(h))
+            with phase("strip.reduced_solve_T"):
+                rhs = torch.zeros((G + 1, m), dtype=torch.float64, device=self.device)
+                rhs[:-1] += H[:, 0]
+                rhs[1:] += H[:, 1]
+                return self._red._cr_solve_T(rhs)[self.rank:self.rank + 2].reshape(-1)
+        with phase("strip.reduced_solve_T"):
+            c = torch.empty((G + 1) * m, dtype=torch.float64, device=self.device)
+            _gemv_t(self._Z, h.reshape(-1), c)
+        with phase("strip.allreduce_T"):
+            t = c.to(self.gather_device)     # in place on the device under RCCL, through the host under gloo
+            self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group)
+            c = t.to(self.device)
+        return c[self.rank * m:(self.rank + 2) * m]
+
+    def _capture_agreed(self, s):
+        """Graph capture of the solve of direction s ("" or "_T"): only when the reduced system's collective runs on
+        the device (RCCL, capturable); under gloo it goes through the host, so the solve stays eager.
         Under RCCL the captured graph is checked against the eager solve before it is used."""
         if self.G > 1 and (self.gather_device.type != "cuda" or os.environ.get("SEM_STRIP_GRAPH", "1") == "0"):
+            if s:
+                self._require_T()
             return False
-        captured = super().capture()       # a capture executes no collective: a failure desynchronises no rank
+        captured = getattr(super(), "capture" + s)()   # a capture executes no collective: a failure desynchronises no rank
         if self.G == 1:
             return captured
         if not self._agree(captured):
-            self._graph = None
+            setattr(self, "_graph" + s, None)
             return False
+        bin_, graph = getattr(self, "_bin" + s), getattr(self, "_graph" + s)
         g = torch.Generator(device=self.device).manual_seed(11)
-        b = torch.rand(self._bin.shape, dtype=torch.float64, device=self.device, generator=g)
-        want = self._solve_lines(b.clone())
-        self._bin.copy_(b)
-        self._graph.replay()           # every rank replays: its all-gather needs every rank
-        err = (self._xout - want).abs().max() / want.abs().max().clamp(min=1e-300)
+        b = torch.rand(bin_.shape, dtype=torch.float64, device=self.device, generator=g)
+        want = getattr(self, "_solve_lines" + s)(b.clone())
+        bin_.copy_(b)
+        graph.replay()                 # every rank replays: its collective needs every rank
+        err = (getattr(self, "_xout" + s) - want).abs().max() / want.abs().max().clamp(min=1e-300)
         if not self._agree(bool(err <= 1e-12)):
-            self._graph = None
+            setattr(self, "_graph" + s, None)
             return False
         return True
+
+    def capture(self):
+        return self._capture_agreed("")
+
+    def capture_T(self):
+        """capture's twin for the transposed solve, under the same rules."""
+        return self._capture_agreed("_T")
 
     def _agree(self, ok):
         """True when every rank reports ok (one all-reduce; every rank takes the same decision)."""
@@ -182,12 +223,16 @@ class _StripReduced:
 
 class StripLineSolver(_StripReduced, VelocityJacobianSolver):
     """x = J^-1 b for a Jacobian whose element columns are strip-partitioned across the ranks of `dist`, each strip
-    condensed by lines (module docstring)."""
+    condensed by lines (module docstring); with adjoint=True also x = J^-T b from the same factor."""
 
-    def __init__(self, P, nex, ney, device, bounds, rank, dist, group=None, ncomp=2, gather_device=None):
+    def __init__(self, P, nex, ney, device, bounds, rank, dist, group=None, ncomp=2, gather_device=None,
+                 adjoint=False):
         """bounds: the StripPartition bounds (rank r holds element columns [bounds[r], bounds[r+1]));
-        gather_device: where the all-gathered blocks travel (the GPU under RCCL, the host under gloo)."""
-        super().__init__(P, bounds[rank + 1] - bounds[rank], ney, device, interior="nested", sweep="auto", ncomp=ncomp)
+        gather_device: where the collectives' buffers travel (the GPU under RCCL, the host under gloo);
+        adjoint: serve solve_T / solve1_T / capture_T / check_refinement_T as well (the forward factor and solve are
+        the same with or without it; every rank must pass the same value)."""
+        super().__init__(P, bounds[rank + 1] - bounds[rank], ney, device, interior="nested", sweep="auto", ncomp=ncomp,
+                         transpose=bool(adjoint))
         self._strip_init(nex, bounds, rank, dist, group, gather_device)
 
     # ------------------------------------------------------------------ factor
@@ -211,6 +256,7 @@ class StripLineSolver(_StripReduced, VelocityJacobianSolver):
         n, m = self.nex, self.m
         dev, f64 = self.device, torch.float64
         inv = pivot_inverse
+        self._aIBp = self._aBIp = self._graph_T = None    # a new factor: the transposed solve's tables are stale
         if n == 1:
             R = torch.stack((torch.stack((S_diag[0], S_up[0])), torch.stack((S_lo[0], S_diag[1]))))
             self._T = None
@@ -290,4 +336,38 @@ class StripLineSolver(_StripReduced, VelocityJacobianSolver):
                 X01 = self._T[1]
                 out[1:n] = y
                 _gemv(X01.view(-1, X01.shape[-1]), xb2, out[1:n].reshape(-1), alpha=-1.0, beta=1.0)
+        return out
+
+    def _thomas_T(self, g):
+        """y = T^-T g for the local interior lines (g: (k, m), not modified): the transposed sweeps on the forward
+        sweep's operators."""
+        form, op = self._T[0]
+        return twisted_thomas_solve_T(op, g) if form == "twisted" else fused_thomas_solve_T(*op, g)
+
+    def _iface_solve_T(self, g):
+        """The transposed interface system S^T x = g over the strips (g is not modified), from the operators the
+        forward factor keeps: with S_ib the interior lines' couplings to the two boundary lines and X01 = T^-1 S_ib,
+        h = g_b - X01^T g_int, R^T x_b = h (reduced, shared), x_int = T^-T (g_int - S_bi^T x_b), where S_bi^T x_b is
+        S_up0^T x_0 on line 1 and S_lon^T x_n on line n - 1.  No host synchronisation under RCCL."""
+        if self.G == 1:
+            return super()._iface_solve_T(g)
+        n, m = self.nex, self.m
+        with phase("strip.back_substitution_T"):
+            h = torch.stack((g[0], g[n]))
+            if self._T is not None:   # the transpose of the back substitution: one GEMV over the (k m) x 2m view
+                X01 = self._T[1]
+                _gemv_t(X01.view(-1, X01.shape[-1]), g[1:n].reshape(-1), h.view(-1), alpha=-1.0, beta=1.0)
+        xb2 = self._reduced_solve_T(h)
+        out = torch.empty_like(g)
+        out[0], out[n] = xb2[:m], xb2[m:]
+        if self._T is not None:
+            with phase("strip.interior_sweep_T"):
+                r = g[1:n].clone()
+                x0, xn = out[0], out[n]
+                if n > 2:
+                    _gemv2_t((self._S_up0, x0, r[0]), (self._S_lon, xn, r[-1]), alpha=-1.0, beta=1.0)
+                else:         # one interior line takes both products: two ordered launches, never one dual launch
+                    _gemv_t(self._S_up0, x0, r[0], alpha=-1.0, beta=1.0)
+                    _gemv_t(self._S_lon, xn, r[0], alpha=-1.0, beta=1.0)
+                out[1:n] = self._thomas_T(r)
         return out

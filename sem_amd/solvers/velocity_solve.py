@@ -363,63 +363,134 @@ def fused_thomas_solve(D0, F, Uh, g):
 
 
 # ---- transposed interface sweeps: x = S^-T b from the forward sweeps' stored operators.  Every forward sweep is a
-# list of steps y (+)= alpha A x; its transpose is the same list backwards, each step x_bar += alpha A^T y_bar
-# (torch products with .mT: the Thomas forms have no transposed HIP kernel and are not tuned).  b is not modified.
+# list of steps y (+)= alpha A x; its transpose is the same list backwards, each step x_bar += alpha A^T y_bar: one
+# streaming transposed GEMV (sem_gemv_rows_t on the GPU, A.mT @ x elsewhere) per step.  b is not modified.
+
+GEMV_T_FORM = 0   # sem_gemv_rows_t's form: 0 by size, 1 wide, 2 narrow (tools/strip_solve_T_probe.py sets it for A/B)
+
+
+def _axpby(t, y, alpha, beta):
+    """y = alpha t + beta y in place, the plain forms written as the single torch operation they are."""
+    if beta == 0.0:
+        y.copy_(t if alpha == 1.0 else alpha * t)
+    elif beta == 1.0 and alpha == 1.0:
+        y += t
+    elif beta == 1.0 and alpha == -1.0:
+        y -= t
+    else:
+        y.mul_(beta).add_(t, alpha=alpha)
+    return y
+
+
+def _gemv_t(A, x, y, alpha=1.0, beta=0.0):
+    """y = alpha A^T x + beta y for a row-major operator A (rows x columns; x: rows, y: columns): _gemv's twin on
+    sem_gemv_rows_t, torch elsewhere."""
+    if A.is_cuda and _SWEEP_GEMV == "hip" and A.dtype == torch.float64 and A.stride(1) == 1 and x.stride(0) == 1 \
+            and y.stride(0) == 1:
+        import ctypes as C
+        from .. import _lib
+        lib = _lib.load()
+        _lib.check(lib.sem_gemv_rows_t(A.shape[0], A.shape[1], alpha, C.c_void_p(A.data_ptr()), A.stride(0),
+                                       C.c_void_p(x.data_ptr()), beta, C.c_void_p(y.data_ptr()), GEMV_T_FORM,
+                                       C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)))
+        return y
+    return _axpby(A.mT @ x, y, alpha, beta)
+
+
+def _gemv2_t(p0, p1, alpha=1.0, beta=0.0):
+    """Two independent transposed GEMVs (A, x, y) of equal row count in one launch (sem_gemv_rows2_t); torch
+    elsewhere.  The two y must not overlap."""
+    (A0, x0, y0), (A1, x1, y1) = p0, p1
+    ok = lambda A, x, y: (A.is_cuda and A.dtype == torch.float64 and A.stride(1) == 1  # noqa: E731
+                          and x.stride(0) == 1 and y.stride(0) == 1)
+    if _SWEEP_GEMV == "hip" and A0.shape[0] == A1.shape[0] and ok(A0, x0, y0) and ok(A1, x1, y1):
+        import ctypes as C
+        from .. import _lib
+        lib = _lib.load()
+        v = C.c_void_p
+        _lib.check(lib.sem_gemv_rows2_t(A0.shape[0], alpha, beta, A0.shape[1], v(A0.data_ptr()), A0.stride(0),
+                                        v(x0.data_ptr()), v(y0.data_ptr()), A1.shape[1], v(A1.data_ptr()),
+                                        A1.stride(0), v(x1.data_ptr()), v(y1.data_ptr()), GEMV_T_FORM,
+                                        v(torch.cuda.current_stream(A0.device).cuda_stream)))
+        return
+    _gemv_t(A0, x0, y0, alpha, beta)
+    _gemv_t(A1, x1, y1, alpha, beta)
+
 
 def plain_thomas_solve_T(Dinv, S_lo, Uh, b):
     """x = S^-T b from the plain block-Thomas factors (the transpose of _iface_solve's last form)."""
     n = b.shape[0]
     z = b.clone()
     for L in range(n - 1):                       # the back substitution x_L -= Uh_L x_{L+1}, reversed
-        z[L + 1] -= Uh[L].mT @ z[L]
+        _gemv_t(Uh[L], z[L], z[L + 1], alpha=-1.0, beta=1.0)
     g = torch.empty_like(b)
     for L in range(n - 1, 0, -1):                # z_L = Dinv_L (g_L - S_lo[L-1] z_{L-1}), reversed
-        g[L] = Dinv[L].mT @ z[L]
-        z[L - 1] -= S_lo[L - 1].mT @ g[L]
-    g[0] = Dinv[0].mT @ z[0]
+        _gemv_t(Dinv[L], z[L], g[L])
+        _gemv_t(S_lo[L - 1], g[L], z[L - 1], alpha=-1.0, beta=1.0)
+    _gemv_t(Dinv[0], z[0], g[0])
     return g
 
 
 def fused_thomas_solve_T(D0, F, Uh, b):
-    """x = S^-T b from fused_thomas_operators (the transpose of fused_thomas_solve)."""
+    """x = S^-T b from fused_thomas_operators (the transpose of fused_thomas_solve).  Work rows W[L] = [0 | z_L]:
+    F_L^T z_{L+1} = [g_{L+1} | the update of z_L] is added to row L whole, so every step is one product and no
+    slice-and-add follows it (fused_thomas_solve's layout, mirrored); row L's first half ends as g_{L+1}."""
     n, m = b.shape[0], b.shape[1]
-    z = b.clone()
+    W = torch.zeros((n, 2 * m), dtype=b.dtype, device=b.device)
+    W[:, m:] = b
+    z = W[:, m:]
     for L in range(n - 1):
-        z[L + 1] -= Uh[L].mT @ z[L]
-    g = torch.empty_like(b)
+        _gemv_t(Uh[L], z[L], z[L + 1], alpha=-1.0, beta=1.0)
     for L in range(n - 1, 0, -1):                # z_L = F_{L-1} [g_L; z_{L-1}], reversed
-        v = F[L - 1].mT @ z[L]
-        g[L] = v[:m]
-        z[L - 1] += v[m:]
-    g[0] = D0.mT @ z[0]
+        _gemv_t(F[L - 1], z[L], W[L - 1], beta=1.0)
+    g = torch.empty_like(b)
+    _gemv_t(D0, z[0], g[0])
+    g[1:] = W[:n - 1, :m]
     return g
 
 
 def twisted_thomas_solve_T(op, b):
     """x = S^-T b from twisted_thomas_operators (the transpose of twisted_thomas_solve): the two back chains
-    reversed (they meet at line k), the middle step, then the two forward chains reversed."""
+    reversed (they meet at line k), the middle step, then the two forward chains reversed.  Work rows as the forward
+    sweep's, W[L] = [0 | s_L | t_L]: z_L of a top line lives in the slot s_{L+1}, of a bottom line in s_{L-1} (t_k
+    for line k + 1), so F_L^T z_L = [g_L | the update of the chain's next z] is added to row L whole.  The two
+    chains' steps share a launch (sem_gemv_rows2_t) except where both write line k."""
     k, D0, E0, FT, FB, FM, UhT, UhB = op
     n, m = b.shape[0], b.shape[1]
-    z = b.clone()
-    for L in range(n - 1, k, -1):                # x_L = w_L - UhB_L x_{L-1}, reversed
-        z[L - 1] -= UhB[L - (k + 1)].mT @ z[L]
-    for L in range(k):                           # x_L = z_L - UhT_L x_{L+1}, reversed
-        z[L + 1] -= UhT[L].mT @ z[L]
+    W = torch.zeros((n, 3 * m), dtype=b.dtype, device=b.device)
+    top = lambda L: W[L + 1, m:2 * m]                                        # noqa: E731  z_L, L < k
+    bot = lambda L: W[k, 2 * m:] if L == k + 1 else W[L - 1, m:2 * m]        # noqa: E731  z_L, L > k
+    W[1:k + 1, m:2 * m] = b[:k]
+    W[k, 2 * m:] = b[k + 1]
+    W[k + 1:n - 1, m:2 * m] = b[k + 2:]
+    zk = b[k].clone()
+
+    def both(pt, pb, **kw):
+        if pt and pb:
+            _gemv2_t(pt, pb, **kw)
+        elif pt or pb:
+            _gemv_t(*(pt or pb), **kw)
+
+    # the back chains reversed: x_L = w_L - UhB_L x_{L-1} (L = n-1 .. k+1) beside x_L = z_L - UhT_L x_{L+1}
+    # (L = 0 .. k-1); the last step of each writes line k: those two run one after the other
+    steps_b, steps_t = list(range(n - 1, k + 1, -1)), list(range(k - 1))
+    for j in range(max(len(steps_b), len(steps_t))):
+        Lb = steps_b[j] if j < len(steps_b) else None
+        Lt = steps_t[j] if j < len(steps_t) else None
+        both((UhT[Lt], top(Lt), top(Lt + 1)) if Lt is not None else None,
+             (UhB[Lb - (k + 1)], bot(Lb), bot(Lb - 1)) if Lb is not None else None, alpha=-1.0, beta=1.0)
+    _gemv_t(UhB[0], bot(k + 1), zk, alpha=-1.0, beta=1.0)
+    _gemv_t(UhT[k - 1], top(k - 1), zk, alpha=-1.0, beta=1.0)
+    _gemv_t(FM, zk, W[k], beta=1.0)              # x_k = FM [g_k; z_{k-1}; w_{k+1}], reversed
+    steps_t, steps_b = list(range(k - 1, 0, -1)), list(range(k + 1, n - 1))
+    for j in range(max(len(steps_t), len(steps_b))):
+        Lt = steps_t[j] if j < len(steps_t) else None
+        Lb = steps_b[j] if j < len(steps_b) else None
+        both((FT[Lt - 1], top(Lt), W[Lt, :2 * m]) if Lt is not None else None,
+             (FB[Lb - (k + 1)], bot(Lb), W[Lb, :2 * m]) if Lb is not None else None, beta=1.0)
     g = torch.empty_like(b)
-    v = FM.mT @ z[k]                             # x_k = FM [g_k; z_{k-1}; w_{k+1}]
-    g[k] = v[:m]
-    z[k - 1] += v[m:2 * m]
-    z[k + 1] += v[2 * m:]
-    for L in range(k - 1, 0, -1):
-        v = FT[L - 1].mT @ z[L]
-        g[L] = v[:m]
-        z[L - 1] += v[m:]
-    g[0] = D0.mT @ z[0]
-    for L in range(k + 1, n - 1):
-        v = FB[L - (k + 1)].mT @ z[L]
-        g[L] = v[:m]
-        z[L + 1] += v[m:]
-    g[n - 1] = E0.mT @ z[n - 1]
+    _gemv2_t((D0, top(0), g[0]), (E0, bot(n - 1), g[n - 1]))
+    g[1:n - 1] = W[1:n - 1, :m]
     return g
 
 
@@ -1399,14 +1470,14 @@ class VelocityJacobianSolver:
                 and getattr(self, "hip_nested", True)):
             return self._solve_lines_hip_T(B)   # (a factor on the dense edge inverse takes the torch path below)
         cBI, cIB = self._line_couplings()
-        return self._condense_torch(B, self._nested_solve_T, self._iface_solve_T, cIB, cBI)
+        return self._condense_torch(B, self._nested_solve_T, self._iface_solve_T, cIB, cBI, own_rhs=self._own_rhs)
 
     def _solve_lines_hip_T(self, B):
         """_solve_lines_once_T on the GPU: the "full" path of the forward solve with sem_nested_solve_t
         (ns_condense_transpose.hip), the permuted couplings and the transposed interface sweep."""
         from .. import _lib
         return self._condense_hip(B, _lib.load().sem_nested_solve_t, self._iface_solve_T, self._aIBp, self._aBIp,
-                                  "vsolve_T")
+                                  "vsolve_T", own_rhs=self._own_rhs)
 
     # ------------------------------------------------------------------ the solve driver
     # One implementation per entry point for both directions, named by the suffix s: "" for J x = b, "_T" for
