@@ -289,6 +289,22 @@ int sem_interface_pack(sem_handle* h, const double* y, const int* bounds, int G,
 int sem_interface_unpack(sem_handle* h, const double* buf, const int* bounds, int G, double* y,
                          void* stream);
 
+/* The same exchange for a buffer in the solvers' LINE layout (entry points added at ABI 15): Y holds the handle's own lines, row
+ * pitch `pitch` doubles, the first and the last line the two interface lines, each `width` <= pitch
+ * entries long (width = 2 N_y for a [u | v] velocity line: both components of both lines in one
+ * launch).  cols == NULL (ncols = 0): whole lines, buf has (G-1)*width entries, slot s holding
+ * partition boundary s as in sem_interface_pack; slots this handle does not touch are zero-filled,
+ * so a sum all-reduce assembles.  cols != NULL: a device array of ncols >= 1 in-line offsets, only
+ * those entries are packed and unpacked (buf: (G-1)*ncols entries, slot-major) and the rest of the
+ * lines is left alone.  The offsets must lie in [0, width): they live in device memory and are NOT
+ * checked here -- the caller's duty (sem_amd.device.Mesh checks its host copy).  G < 2: no-op.
+ * SEM_EINVAL: a null Y / buf / handle, width < 1, pitch < width, ncols inconsistent with cols, and
+ * the partition checks of sem_interface_pack; nothing is launched then. */
+int sem_interface_pack_lines(sem_handle* h, const double* Y, int64_t width, int64_t pitch, const int* cols,
+                             int ncols, const int* bounds, int G, double* buf, void* stream);
+int sem_interface_unpack_lines(sem_handle* h, const double* buf, int64_t width, int64_t pitch, const int* cols,
+                               int ncols, const int* bounds, int G, double* Y, void* stream);
+
 /* ---- Krylov-basis sweeps (device GMRES, sem_amd/krylov.py) ------------- */
 /* Replace the Arnoldi orthogonalisation of the reference's LGMRES
  * (ConvectionDiffusion_Solver.py:146-148, NavierStokes_Solver.py:222-224; SciPy's

@@ -77,6 +77,36 @@ __global__ void iface_unpack_kernel(const double* __restrict__ buf, double* __re
   }
 }
 
+// The line-layout twins of the two kernels above: Y holds the handle's lines with row pitch `pitch`, the two interface
+// lines at offsets 0 and right_off; n entries per line are exchanged, the in-line offsets cols[0..n) (cols == nullptr:
+// 0..n-1, the whole line -- every component of a [u | v] line in the one launch).
+__global__ void iface_pack_lines_kernel(const double* __restrict__ Y, double* __restrict__ buf, int64_t n,
+                                        const int* __restrict__ cols, int nslots, int left_slot, int right_slot,
+                                        int64_t right_off) {
+  const int64_t total = static_cast<int64_t>(nslots) * n;
+  for (int64_t t = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; t < total;
+       t += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int s = static_cast<int>(t / n);
+    const int64_t c = t - s * n;
+    const int64_t off = cols ? cols[c] : c;
+    double v = 0.0;
+    if (s == left_slot) v = Y[off];
+    if (s == right_slot) v = Y[right_off + off];
+    buf[t] = v;
+  }
+}
+
+__global__ void iface_unpack_lines_kernel(const double* __restrict__ buf, double* __restrict__ Y, int64_t n,
+                                          const int* __restrict__ cols, int left_slot, int right_slot,
+                                          int64_t right_off) {
+  for (int64_t c = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; c < n;
+       c += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t off = cols ? cols[c] : c;
+    if (left_slot >= 0) Y[off] = buf[left_slot * n + c];
+    if (right_slot >= 0) Y[right_off + off] = buf[right_slot * n + c];
+  }
+}
+
 // SEM.eval_interpolation (SEM.py:248-273): out[a][b] = sum_kl Sx[a][k] u_e[m_a][n_b][k][l] Sy[b][l]
 // for plot rows a (element m_a, evaluation row Sx[a]) and plot columns b; points whose element
 // index is negative (outside the mesh) are left untouched, like the reference's np.place.
@@ -488,6 +518,46 @@ int sem_interface_unpack(sem_handle* h, const double* buf, const int* bounds, in
                      reinterpret_cast<hipStream_t>(stream), buf, y, h->NY, L, static_cast<int64_t>(0), R,
                      h->n_local - h->NY);
   return hip_check(hipGetLastError(), "interface unpack launch");
+}
+
+// the checks the two line-layout entry points share; *n = entries exchanged per line, *right_off = the last line's offset
+static int iface_lines_args(const sem_handle* h, const void* Y, const void* buf, int64_t width, int64_t pitch,
+                            const int* cols, int ncols, const int* bounds, int G, int* left, int* right, int64_t* n,
+                            int64_t* right_off) {
+  if (!h || !Y || !buf) return set_error(SEM_EINVAL, "null argument");
+  if (width < 1) return set_error(SEM_EINVAL, "interface lines: width must be at least 1");
+  if (pitch < width) return set_error(SEM_EINVAL, "interface lines: pitch must be at least width");
+  if (cols ? ncols < 1 : ncols != 0)
+    return set_error(SEM_EINVAL, "interface lines: ncols must be >= 1 with a column list and 0 without one");
+  if (int st = iface_slots(h, bounds, G, left, right)) return st;
+  *n = cols ? ncols : width;
+  *right_off = (h->line_end - h->line_begin) * pitch;   // line_end is the last line itself
+  return SEM_OK;
+}
+
+int sem_interface_pack_lines(sem_handle* h, const double* Y, int64_t width, int64_t pitch, const int* cols, int ncols,
+                             const int* bounds, int G, double* buf, void* stream) {
+  int L, R, st;
+  int64_t n, roff;
+  if ((st = iface_lines_args(h, Y, buf, width, pitch, cols, ncols, bounds, G, &L, &R, &n, &roff))) return st;
+  if (G < 2) return SEM_OK;
+  if ((st = on_device(h))) return st;
+  const int64_t total = static_cast<int64_t>(G - 1) * n;
+  hipLaunchKernelGGL(iface_pack_lines_kernel, dim3(grid_for(total, 256)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), Y, buf, n, cols, G - 1, L, R, roff);
+  return hip_check(hipGetLastError(), "interface lines pack launch");
+}
+
+int sem_interface_unpack_lines(sem_handle* h, const double* buf, int64_t width, int64_t pitch, const int* cols,
+                               int ncols, const int* bounds, int G, double* Y, void* stream) {
+  int L, R, st;
+  int64_t n, roff;
+  if ((st = iface_lines_args(h, Y, buf, width, pitch, cols, ncols, bounds, G, &L, &R, &n, &roff))) return st;
+  if (G < 2) return SEM_OK;
+  if ((st = on_device(h))) return st;
+  hipLaunchKernelGGL(iface_unpack_lines_kernel, dim3(grid_for(n, 256)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), buf, Y, n, cols, L, R, roff);
+  return hip_check(hipGetLastError(), "interface lines unpack launch");
 }
 
 }  // extern "C"

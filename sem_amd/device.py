@@ -184,6 +184,51 @@ class Mesh:
         _lib.check(self._lib.sem_interface_unpack(self._h, _ptr(buf), b, len(bounds) - 1, _ptr(y),
                                                   self.stream_ptr(stream)))
 
+    def _lines_args(self, Y, buf, bounds, cols, width):
+        """The host checks of interface_pack_lines / interface_unpack_lines: Y the handle's lines as a 2-D float64
+        view with unit column stride (row pitch = its row stride), `width` entries per line exchanged (default: the
+        view's row length), cols a sequence of in-line offsets in [0, width) or None (whole lines), buf large
+        enough for every slot.  The offsets are checked here, on the host, and kept on the device per distinct list
+        (the library does not read them back).  Returns the C arguments between the handle and the buffer."""
+        lines = self.line_end - self.line_begin + 1
+        if (not isinstance(Y, torch.Tensor) or Y.device != self.device or Y.dtype != torch.float64 or Y.dim() != 2
+                or Y.shape[0] != lines or (Y.shape[1] > 1 and Y.stride(1) != 1)):
+            raise ValueError(f"Y must be a float64 ({lines}, width) line array on {self.device} with unit column stride")
+        width = Y.shape[1] if width is None else int(width)
+        pitch = Y.stride(0)
+        if not 1 <= width <= Y.shape[1] or pitch < width:
+            raise ValueError("interface lines: need 1 <= width <= the row length <= the row pitch")
+        n, cptr = width, None
+        if cols is not None:
+            key = tuple(int(c) for c in cols)
+            if not key or min(key) < 0 or max(key) >= width:
+                raise ValueError("interface lines: cols must be a non-empty list of offsets in [0, width)")
+            cache = self.__dict__.setdefault("_line_cols", {})
+            if key not in cache:
+                cache[key] = torch.tensor(key, dtype=torch.int32, device=self.device)
+            n, cptr = len(key), _ptr(cache[key])
+        G = len(bounds) - 1
+        if (not isinstance(buf, torch.Tensor) or buf.device != self.device or buf.dtype != torch.float64
+                or not buf.is_contiguous() or buf.numel() < (G - 1) * n):
+            raise ValueError(f"buf must be a contiguous float64 tensor of at least {(G - 1) * n} entries on {self.device}")
+        b = (C.c_int * len(bounds))(*bounds)
+        return width, pitch, cptr, (0 if cols is None else n), b, G
+
+    def interface_pack_lines(self, Y, bounds, buf, cols=None, width=None, stream=None):
+        """sem_interface_pack_lines: the two interface lines of the line-layout array Y (first and last row; every
+        component of a [u | v] line at once) into buf's slots, zeros in the slots of other boundaries; with cols only
+        those in-line offsets.  A sum all-reduce of buf and interface_unpack_lines assemble Y's shared lines."""
+        w, pitch, cptr, nc, b, G = self._lines_args(Y, buf, bounds, cols, width)
+        _lib.check(self._lib.sem_interface_pack_lines(self._h, _ptr(Y), w, pitch, cptr, nc, b, G, _ptr(buf),
+                                                      self.stream_ptr(stream)))
+
+    def interface_unpack_lines(self, buf, bounds, Y, cols=None, width=None, stream=None):
+        """sem_interface_unpack_lines: buf's slots of this handle's boundaries back onto Y's first / last row (with
+        cols: only those offsets; everything else in Y is left alone)."""
+        w, pitch, cptr, nc, b, G = self._lines_args(Y, buf, bounds, cols, width)
+        _lib.check(self._lib.sem_interface_unpack_lines(self._h, _ptr(buf), w, pitch, cptr, nc, b, G, _ptr(Y),
+                                                        self.stream_ptr(stream)))
+
     def _velocity_desc(self, c_mass, c_stiff, c_gradx, c_grady, cu, cv, juu, juv, jvu, jvv, dir_mask, dir_sides, ncomp,
                        cols):
         """The checks and the SemVelocityDesc of the two block writers; returns (descriptor, c0, c1)."""

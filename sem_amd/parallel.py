@@ -85,6 +85,23 @@ class InterfaceExchange:
             self.mesh.interface_unpack(self._mbuf[i * n:(i + 1) * n], self.part.bounds, y)
         return ys
 
+    def lines(self, Y, cols=None):
+        """Assemble the two interface lines of a LINE-layout array Y ((lines, width) view of this strip, e.g. the
+        velocity solve's [u | v] lines) in place: one pack launch for every component of both lines
+        (Mesh.interface_pack_lines), ONE all-reduce, one unpack -- with a buffer of its own per payload size, so an
+        exchange started with start() is not disturbed.  cols: only those in-line offsets."""
+        if self.part.world == 1:
+            return Y
+        n = Y.shape[1] if cols is None else len(cols)
+        bufs = self.__dict__.setdefault("_lbuf", {})
+        buf = bufs.get(n)
+        if buf is None:
+            buf = bufs[n] = torch.empty((self.part.world - 1) * n, dtype=torch.float64, device=self.mesh.device)
+        self.mesh.interface_pack_lines(Y, self.part.bounds, buf, cols=cols)
+        self.dist.all_reduce(buf, group=self.group)
+        self.mesh.interface_unpack_lines(buf, self.part.bounds, Y, cols=cols)
+        return Y
+
 
 class NeighborExchange:
     """Interface assembly by point-to-point exchange with the two neighbouring strips."""
@@ -138,6 +155,29 @@ class NeighborExchange:
         for y in ys:
             self(y)
         return ys
+
+    def lines(self, Y, cols=None):
+        """InterfaceExchange.lines by point-to-point exchange: the first / last row of the line-layout array Y (with
+        cols: those in-line offsets of them) goes to the left / right neighbour and what arrives is added."""
+        if self.part.world == 1:
+            return Y
+        d = self.dist
+        idx = slice(None) if cols is None else torch.as_tensor(list(cols), device=Y.device)
+        bdev = "cpu" if self.host else Y.device
+        ops, recv = [], []
+        for peer, row in ((self.left, 0), (self.right, -1)):
+            if peer is None:
+                continue
+            send = Y[row, idx].to(bdev).contiguous()
+            got = torch.empty_like(send)
+            ops.append(d.P2POp(d.isend, send, self._peer(peer), self.group))
+            ops.append(d.P2POp(d.irecv, got, self._peer(peer), self.group))
+            recv.append((row, got))
+        for req in (d.batch_isend_irecv(ops) if ops else []):
+            req.wait()
+        for row, got in recv:
+            Y[row, idx] += got.to(Y.device)
+        return Y
 
 
 class StripApply:
@@ -304,6 +344,14 @@ class Partition:
         if ex is not None:
             ex.many(list(ys))
         return ys
+
+    def assemble_lines(self, Y, cols=None):
+        """assemble for a strip's LINE-layout array Y ((lines, width), e.g. the velocity solve's [u | v] lines), in
+        place: its two interface lines summed with the neighbours' (cols: only those in-line offsets)."""
+        ex = self.step.exch
+        if ex is not None:
+            ex.lines(Y, cols)
+        return Y
 
     def backend_device(self):
         """Where collective buffers live: the GPU under RCCL ("nccl"), the host under gloo."""

@@ -36,6 +36,8 @@ from .velocity_solve import VelocityJacobianSolver
 
 
 _ALL_SIDES = _lib.SIDE_W | _lib.SIDE_E | _lib.SIDE_S | _lib.SIDE_N
+_NEEDS_ND = ("NavierStokes: velocity_solve_T needs the nested-dissection factor (P >= 2, the whole perimeter Dirichlet, "
+             "velocity_interior 'auto' or 'nd'): the line condensation has no transposed solve")
 
 
 class _SchurVariant(typing.NamedTuple):
@@ -58,6 +60,7 @@ class _SchurVariant(typing.NamedTuple):
 
 class NavierStokesSolver(SolverBase):
     _name, _whole_mesh_note = "NavierStokes", " (no transposed strip solve)"
+    _partition_adjoint_modes = ("distributed",)
 
     def __init__(self, L_x: float, L_y: float, Re: float, Gr: float, P: int, N_ex: int, N_ey: int,
                  v_W: float = 0, v_E: float = 0, u_S: float = 0, u_N: float = 0,
@@ -81,6 +84,11 @@ class NavierStokesSolver(SolverBase):
         solves, the result is broadcast; a distributed adjoint Schur solve waits for the transposed strip solvers.
         velocity_solve_T and _velocity_apply_lines_T stay whole-mesh only.  Off by default: a partitioned solver
         refuses every reverse-mode method.
+        partition_adjoint="distributed": as True, but _get_update_T runs on the strips -- the strip velocity factor
+        is built with its transposed solve (nested_dissection.StripNDSolver(adjoint=True); the nested-dissection
+        factor only, schur_precond='mass'), velocity_solve_T and _velocity_apply_lines_T work on the strips, and the
+        adjoint Schur system S^T q = E^T q - B^T J^-T C^T q is solved over the strips (_StripSchurT) by the GMRES
+        with all-reduced inner products: no whole-mesh vector travels and no rank waits for rank 0.
         recycle_bytes: device memory for a recycled Krylov subspace of the Schur-complement solves
         (sem_amd.krylov.Recycle, GCRO; 0 = off, the default): consecutive _get_update calls with one
         linearisation -- the Boussinesq coupler's block-Jacobi preconditioner -- then start from the
@@ -293,6 +301,10 @@ class NavierStokesSolver(SolverBase):
                              lambda twin, bu, bv, bp, q0: twin._get_update_T(bu, bv, bp, dres_c0=q0),
                              (du_bar, dv_bar, dp_bar, dres_c0), 3, "schur_matvecs", "the adjoint update")
 
+    def _dist_adjoint(self):
+        """True on a partitioned solver built with partition_adjoint='distributed'."""
+        return self._part is not None and self._partition_adjoint_mode == "distributed"
+
     def _use_nd(self):
         """Nested dissection (velocity_interior "auto" / "nd") needs P >= 2 and the whole perimeter Dirichlet."""
         ok = self._P >= 2 and self._dir.mask is None and self._dir.sides == _ALL_SIDES
@@ -312,8 +324,10 @@ class NavierStokesSolver(SolverBase):
         m, p = self._mesh, self._part
         # every rank takes the same choice: the Dirichlet set and the option are global
         cls = StripNDSolver if self._use_nd() else StripLineSolver
+        # the distributed adjoint update needs the factor's transposed solve (the forward factor is the same)
+        extra = dict(adjoint=True) if cls is StripNDSolver and self._dist_adjoint() else {}
         vs = cls(self._P, self._N_ex, self._N_ey, m.device, p.part.bounds, p.rank, p.dist, group=p.group,
-                 gather_device=p.backend_device())
+                 gather_device=p.backend_device(), **extra)
         vs.factor_mesh(m, dir_mask=self._dir.mask, dir_sides=self._dir.sides, **self._jac_kw)
         vs.set_operator(self._velocity_apply_lines, amax=lambda t: p.amax(t))
         vs.check_refinement()       # every rank takes the same decision (norms max-reduced over the ranks)
@@ -404,7 +418,18 @@ class NavierStokesSolver(SolverBase):
             u block: (Sys + diag(juu))_D^T z_u + jvu z'_v,    v block: (Sys + diag(jvv))_D^T z_v + juv z'_u
         -- two fused transposed launches (sem_apply_transpose, identity Dirichlet rows), the cross terms pre-loaded
         into the outputs and added through c_acc = 1.  The operator of check_refinement_T and of the transposed
-        velocity solve's refinement step.  Whole mesh only; sem_apply_transpose refuses what it does not support."""
+        velocity solve's refinement step.  sem_apply_transpose refuses what it does not support.
+        On the strips (partition_adjoint='distributed'; X this strip's lines, equal on shared lines): ONE
+        sem_ns_apply_transpose_part launch on line views of X and of the result -- the velocity block of the strip's
+        own A_s^T at z_c = 0, which is the same operator: the Dirichlet rows of [J C] are identity rows, so
+        (A^T [z_u; z_v; 0])_{u,v} = J_D^T z, cross terms included -- and the interface lines of the line buffer
+        summed across the strips (Partition.assemble_lines).  Otherwise whole mesh only."""
+        if self._dist_adjoint():
+            m, NY = self._mesh, self._mesh.NY
+            Y = torch.empty_like(X)
+            m.ns_apply_transpose_part(X[:, :NY], X[:, NY:], None, Y[:, :NY], Y[:, NY:], None, **self._jac_kw,
+                                      **self._ns_kw(pin_first=False))
+            return self._part.assemble_lines(Y)
         self._whole_mesh_only("_velocity_apply_lines_T")
         m, NY = self._mesh, self._mesh.NY
         kw = self._jac_kw
@@ -420,11 +445,40 @@ class NavierStokesSolver(SolverBase):
         """(J^-T [bu; bv]) split as (xu, xv) from the cached nested-dissection factor of _velocity_solver() -- the
         inner solve of a transposed Schur matvec S_p^T = G^T J^-T D^T.  The first call after a linearisation
         registers _velocity_apply_lines_T, runs check_refinement_T and, with velocity_graph, captures the transposed
-        solve.  NumPy in, NumPy out; device tensors in, device tensors out.  Whole-mesh solvers whose factor is
-        nested dissection only: there is no transposed line condensation and no transposed strip solve."""
-        self._whole_mesh_only("velocity_solve_T")
-        xu, xv = self._velocity_solver_T().solve_T(self._dev(bu), self._dev(bv))
+        solve.  NumPy in, NumPy out; device tensors in, device tensors out.  Solvers whose factor is nested dissection
+        only (there is no transposed line condensation): whole-mesh ones, and partitioned ones built with
+        partition_adjoint='distributed' -- the transposed strip solve (StripNDSolver(adjoint=True)): local tensors
+        in (equal on shared lines), local tensors out; global NumPy in, gathered NumPy out."""
+        if self._dist_adjoint():
+            vs = self._strip_velocity_solver_T()
+        else:
+            self._whole_mesh_only("velocity_solve_T")
+            vs = self._velocity_solver_T()
+        xu, xv = vs.solve_T(self._dev(bu), self._dev(bv))
         return self._out(xu, bu), self._out(xv, bu)
+
+    def _strip_velocity_solver_T(self):
+        """_velocity_solver_T's twin on the strips: _strip_velocity_solver()'s factor made ready for transposed
+        solves (the transposed operator registered, check_refinement_T -- every rank the same decision, the norms
+        max-reduced --, capture_T attempted: declined while the collectives go through the host).  The same
+        ValueError for a factor that is not nested dissection."""
+        from .nested_dissection import StripNDSolver
+        if self._jac_kw is None:
+            raise RuntimeError("NavierStokes: _get_residuals and _calc_jacobians must run before the transposed "
+                               "velocity solve")
+        if not self._use_nd():
+            raise ValueError(_NEEDS_ND)
+        vs = self._strip_velocity_solver()
+        if not isinstance(vs, StripNDSolver):
+            raise ValueError(_NEEDS_ND)
+        if vs._apply_T is None:
+            p = self._part
+            vs.set_operator(self._velocity_apply_lines, amax=lambda t: p.amax(t),
+                            apply_lines_T=self._velocity_apply_lines_T)
+            vs.check_refinement_T()
+            if self._velocity_graph:
+                vs.capture_T()
+        return vs
 
     def _velocity_solver_T(self):
         """_velocity_solver()'s factor made ready for transposed solves: the first call after a linearisation
@@ -432,9 +486,7 @@ class NavierStokesSolver(SolverBase):
         solve.  ValueError for a factor that is not nested dissection."""
         vs = self._velocity_solver()
         if not isinstance(vs, NestedDissectionSolver):
-            raise ValueError("NavierStokes: velocity_solve_T needs the nested-dissection factor (P >= 2, the whole "
-                             "perimeter Dirichlet, velocity_interior 'auto' or 'nd'): the line condensation has no "
-                             "transposed solve")
+            raise ValueError(_NEEDS_ND)
         if vs._apply_T is None:
             vs.set_operator(self._velocity_apply_lines, apply_lines_T=self._velocity_apply_lines_T)
             vs.check_refinement_T()
@@ -520,9 +572,29 @@ class NavierStokesSolver(SolverBase):
                              progress=True, clock=False, report=True)
 
     def _adjoint_variant(self):
-        """_schur_update's record for _get_update_T on the whole mesh: the transposed solves and launches, plain
-        GMRES over _SchurComplementT, no recycling."""
-        m, kw = self._mesh, self._ns_kw(pin_first=False)
+        """_schur_update's record for _get_update_T: the transposed solves and launches, plain GMRES over
+        _SchurComplementT, no recycling; on the strips (partition_adjoint='distributed') the strip's own transposed
+        launches (sem_ns_apply_transpose_part) each followed by the interface assembly, the transposed strip solve,
+        and the GMRES with all-reduced inner products over _StripSchurT, sized as the forward strip variant."""
+        m, part, kw = self._mesh, self._part, self._ns_kw(pin_first=False)
+        if part is not None:
+            vs = self._strip_velocity_solver_T()
+
+            def strip_pressure_rhs(fu, fv, c0):    # B^T f
+                m.ns_apply_transpose_part(fu, fv, None, yp=c0, **kw)
+                part.assemble(c0)
+
+            def strip_velocity_rhs(q, bu, bv):     # [bu; bv] - C^T q
+                gu, gv = torch.empty_like(q), torch.empty_like(q)
+                m.ns_apply_transpose_part(None, None, q, gu, gv, c_div=-1.0, **kw)
+                part.assemble(gu, gv)
+                return bu + gu, bv + gv
+
+            return _SchurVariant("adjoint GMRES", "adjoint GMRES", vs.solve_T, strip_pressure_rhs, strip_velocity_rhs,
+                                 "_schur_T", lambda: _StripSchurT(self, vs, graph=self._velocity_graph),
+                                 self._mass_precond, part.max_local_dofs(), gmres,
+                                 lambda restart: dict(maxiter=10 * self.N, inner=part.inner),
+                                 progress=False, clock=False, report=False)
         vs = self._velocity_solver_T()
 
         def pressure_rhs(fu, fv, c0):    # B^T f
@@ -627,10 +699,13 @@ class NavierStokesSolver(SolverBase):
         update's mass-diagonal right preconditioner, stopping rule (||r||_2 <= mtol sqrt(N)) and restart; dres_c0 is
         the initial guess of q.  No recycling.  Whole-mesh solvers with the nested-dissection factor and
         schur_precond='mass' only: PCD's A_p^-T would need a transposed line condensation, which does not exist.
-        On a partitioned solver (partition_adjoint=True) the solve runs centrally (_get_update_T_partitioned): the
-        functional path, not the scalable one."""
+        On a partitioned solver with partition_adjoint=True the solve runs centrally (_get_update_T_partitioned): the
+        functional path, not the scalable one.  With partition_adjoint='distributed' it runs on the strips: the same
+        elimination with the transposed strip solve (StripNDSolver(adjoint=True)) and _StripSchurT, the same
+        preconditioner (the pinned row on the rank that holds it), stopping rule and restart sizing as the forward
+        strip update; global NumPy in, gathered NumPy out; local tensors in, local tensors out."""
         self._whole_mesh_only("_get_update_T", adjoint=True)
-        if self._part is not None:
+        if self._part is not None and not self._dist_adjoint():
             return self._get_update_T_partitioned(du_bar, dv_bar, dp_bar, dres_c0)
         if self._schur_precond == "pcd":
             raise ValueError("NavierStokes: _get_update_T needs schur_precond='mass': the PCD preconditioner's A_p^-T "
@@ -705,12 +780,12 @@ class _StripSchur:
         s = torch.cuda.Stream(dev)
         s.wait_stream(cur)
         with torch.cuda.stream(s):
-            want = ns._schur_strips(self.vs, probe)   # warm-up outside the capture (workspaces, communicators)
+            want = self._body(probe)   # warm-up outside the capture (workspaces, communicators)
         cur.wait_stream(s)
         g = torch.cuda.CUDAGraph()
         try:   # a capture executes no collective, so a rank whose capture fails cannot desynchronise the others
             with no_gc(), torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self._out = ns._schur_strips(self.vs, self._x)
+                self._out = self._body(self._x)
             ok = 1.0
         except RuntimeError:
             torch.cuda.synchronize(dev)
@@ -729,12 +804,48 @@ class _StripSchur:
         part.dist.all_reduce(flag, op=part.dist.ReduceOp.MIN, group=part.group)
         return float(flag.item()) == 1.0
 
+    def _body(self, dp):
+        return self.ns._schur_strips(self.vs, dp)
+
     def __call__(self, dp):
         if self._graph is None:
-            return self.ns._schur_strips(self.vs, dp)
+            return self._body(dp)
         self._x.copy_(dp)
         self._graph.replay()
         return self._out.clone()
+
+
+class _StripSchurT(_StripSchur):
+    """The strip-partitioned adjoint Schur-complement operator S^T q = E^T q - B^T J^-T C^T q: _SchurComplementT's
+    body on the strips, under _StripSchur's capture rules (the same code).  The strip's transposed-gradient launch
+    (sem_ns_apply_transpose_part, c_div = -1) writes -C^T q straight into the solve's [u | v] line buffer, whose two
+    interface lines are summed across the strips in the line layout (Partition.assemble_lines: one pack launch for
+    both components of both lines, one collective, one unpack); the transposed strip solve runs on it; the
+    transposed-divergence launch reads the solution's line views and writes yp, assembled as a plain vector.  No
+    field is stacked into or reshaped out of the line layout."""
+
+    def __init__(self, ns, vs, graph=True):
+        m = ns._mesh
+        lines = m.n_local // m.NY
+        self._B = torch.zeros((lines, 2 * m.NY), dtype=torch.float64, device=m.device)
+        super().__init__(ns, vs, graph=graph)
+
+    def _body(self, q):
+        ns, m, part, NY = self.ns, self.ns._mesh, self.ns._part, self.ns._mesh.NY
+        kw = ns._ns_kw(pin_first=False)
+        B = self._B
+        with phase("schur_T.grad_apply"):
+            m.ns_apply_transpose_part(None, None, q, B[:, :NY], B[:, NY:], c_div=-1.0, **kw)
+        with phase("schur_T.grad_assemble"):
+            part.assemble_lines(B)
+        with phase("schur_T.velocity_solve"):
+            X = self.vs._solve_lines_T(B)
+        yp = torch.empty_like(q)
+        with phase("schur_T.div_apply"):
+            m.ns_apply_transpose_part(X[:, :NY], X[:, NY:], q, yp=yp, **kw)
+        with phase("schur_T.div_assemble"):
+            part.assemble(yp)
+        return yp
 
 
 class _SchurComplement:

@@ -41,7 +41,10 @@ what the CPU tests check against SciPy's sparse solve.
 The same factor solves J^T x = b (_solve_lines_once_T under the inherited solve_T, solve1_T, capture_T,
 check_refinement_T): the transposed factors applied in the reverse order over the stored operators (_build_steps_T;
 HIP steps in csrc/front_transpose.hip), no operator stored twice, the plan built on the first transposed solve.
-Whole mesh only: StripNDSolver refuses (no transposed reduced system).
+StripNDSolver serves it too when built with adjoint=True (refusing otherwise): the transposed steps split at the strip's
+root (_nfwd_T), the transposed reduced system over the strip-boundary lines between the halves (_between_T on
+strip_solve._StripReduced._reduced_solve_T), and the Dirichlet end nodes of the shared lines summed over their two
+strips -- at most two collectives per solve (StripNDSolver._solve_lines_once_T).
 """
 import functools
 import math
@@ -50,6 +53,7 @@ import os
 import numpy as np
 import torch
 
+from ..tracing import phase
 from .strip_solve import _StripReduced
 from .velocity_solve import VelocityJacobianSolver, batched_inverse, pivot_inverse
 
@@ -668,6 +672,8 @@ class NestedDissectionSolver(VelocityJacobianSolver):
                 off += s + b
             steps.append(("gemvT", items, self._scatter_plan(np.concatenate(ct), np.concatenate(cs),
                                                              np.concatenate(bt), np.concatenate(bs)), False))
+        # the split at the root (as _nfwd): the steps so far end on the root's boundary, the rest start from it
+        self._nfwd_T = len(steps)
         for depth in sorted(levels):
             items = []
             for fid in levels[depth]:
@@ -1248,11 +1254,18 @@ class StripNDSolver(_StripReduced, NestedDissectionSolver):
     shared line go to its right owner, and the whole outer lines x = 0, 1 are identity rows.
     Solve: the strip's forward steps (lift, leaves, every level up to its root), the reduced solve for the two
     interface lines, the back-substitution steps -- no coupling solutions X0 / X1 are needed (the fronts' V panels
-    carry the interface lines like any ancestor separator)."""
+    carry the interface lines like any ancestor separator).  With adjoint=True also x = J^-T b from the same factor
+    (_solve_lines_once_T)."""
 
-    def __init__(self, P, nex, ney, device, bounds, rank, dist, group=None, ncomp=2, gather_device=None):
+    def __init__(self, P, nex, ney, device, bounds, rank, dist, group=None, ncomp=2, gather_device=None,
+                 adjoint=False):
+        """adjoint: serve solve_T / solve1_T / capture_T / check_refinement_T as well (J^T x = b across the strips,
+        _solve_lines_once_T); the forward factor, plan and solve are the same with or without it, and every rank
+        must pass the same value."""
         NestedDissectionSolver.__init__(self, P, nex, ney, device, ncomp=ncomp, cols=(bounds[rank], bounds[rank + 1]))
         self._strip_init(nex, bounds, rank, dist, group, gather_device)
+        self.adjoint = bool(adjoint)
+        self._end_cols = None
 
     def factor_mesh(self, mesh, budget_bytes=24 << 30, **kw):
         if mesh.ex_begin != self.eb or mesh.ex_end != self.ee:
@@ -1294,11 +1307,9 @@ class StripNDSolver(_StripReduced, NestedDissectionSolver):
         return R.view(2, m, 2, m).permute(0, 2, 1, 3).contiguous()
 
     def _no_transpose(self, *a, **kw):
-        raise NotImplementedError("the strip nested-dissection solve has no transposed solve: no transposed reduced "
-                                  "system over the strip-boundary lines; solve_T needs the whole mesh in one "
-                                  "NestedDissectionSolver")
-
-    solve_T = solve1_T = _solve_lines_T = capture_T = check_refinement_T = _no_transpose
+        raise NotImplementedError("the strip nested-dissection solve has no transposed solve unless it is built with "
+                                  "adjoint=True (the transposed reduced system over the strip-boundary lines); "
+                                  "without it solve_T needs the whole mesh in one NestedDissectionSolver")
 
     def _between(self, W, B):
         if self.G == 1:
@@ -1307,3 +1318,83 @@ class StripNDSolver(_StripReduced, NestedDissectionSolver):
         xb2 = self._reduced_solve(h)
         W[0] = xb2[:self.m]
         W[-1] = xb2[self.m:]
+
+    # ------------------------------------------------------------------ transposed solve (adjoint=True)
+    def _solve_lines_once_T(self, B):
+        """x = J^-T b across the strips: NestedDissectionSolver's transposed steps split at the root (_nfwd_T) --
+        the first half ends with this strip's share of the reduced right-hand side on its two interface lines, the
+        hook _between_T solves the transposed reduced system for them, the second half substitutes back from the
+        root down and ends with the transposed lift onto this strip's Dirichlet nodes -- and the Dirichlet end nodes
+        of the shared lines summed over their two strips (_assemble_ends_T).  At most TWO collectives per solve:
+        the reduced system's (_reduced_solve_T: one all-reduce, or one all-gather with SEM_STRIP_REDUCED=cr) and
+        the end nodes' all-reduce of 2 ncomp (G + 1) doubles; none with one strip, where the result is
+        NestedDissectionSolver's bitwise (the same steps in the same order)."""
+        if self._steps_T is None:
+            self._build_steps_T()
+        Wz = torch.cat((B.reshape(-1), B.new_zeros(1)))
+        run = self._run_hip_T if self.device.type == "cuda" else self._run_T
+        nf = self._nfwd_T
+        run(Wz, 0, nf)
+        W = Wz[:-1].view(self.NX, self.m)
+        self._between_T(W, B)
+        run(Wz, nf, len(self._steps_T))
+        self._assemble_ends_T(W, B)
+        return W
+
+    def _between_T(self, W, B):
+        """_between's twin.  After the first half W holds, on the two interface lines, b minus this strip's share
+        A_I,Gamma^T A_II^-T b_I of the transposed Schur complement's right-hand side (the lines' Dirichlet entries
+        still b: the lift comes last); a shared right line's b is the right owner's, so it is subtracted here and
+        counted once over the ranks.  R's Dirichlet rows and columns are identity, so R^T's are too."""
+        if self.G == 1:
+            return
+        h = torch.stack((W[0], W[-1] if self.own_right else W[-1] - B[-1]))
+        xb2 = self._reduced_solve_T(h)
+        W[0] = xb2[:self.m]
+        W[-1] = xb2[self.m:]
+
+    def _assemble_ends_T(self, W, B):
+        """The transposed lift gives x_D = b_D - A_ND^T x_N from this strip's own elements.  The two end nodes
+        (gy = 0, N_y - 1; every component) of a SHARED line take contributions from the elements of both strips:
+        the non-owner's b_D is taken off, the 2 ncomp values per line are summed over the ranks in one all-reduce of
+        (G + 1) 2 ncomp doubles, and both neighbours read the line's slot: bitwise equal.  (The outer lines x = 0, 1
+        are wholly local; the other Dirichlet nodes of a strip, on y = 0, 1 between its lines, are its own.)"""
+        G, r = self.G, self.rank
+        if G == 1:
+            return
+        if self._end_cols is None:
+            NY = self.NY
+            self._end_cols = torch.as_tensor([c * NY + j for c in range(self.ncomp) for j in (0, NY - 1)],
+                                             device=self.device)
+        cols = self._end_cols
+        e = torch.zeros((G + 1, cols.numel()), dtype=torch.float64, device=self.device)
+        if r > 0:
+            e[r] = W[0, cols]
+        if r < G - 1:
+            e[r + 1] = W[-1, cols] - B[-1, cols]
+        with phase("strip.allreduce_ends_T"):
+            t = e.to(self.gather_device)
+            self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group)
+            e = t.to(self.device)
+        if r > 0:
+            W[0, cols] = e[r]
+        if r < G - 1:
+            W[-1, cols] = e[r + 1]
+
+
+def _adjoint_only(name):
+    """StripNDSolver's transposed entry point `name`: the inherited one when the solver was built with adjoint=True,
+    the refusal otherwise (also for a `self` that is no solver at all: the flag is read before anything else)."""
+    def method(self, *a, **kw):
+        if not getattr(self, "adjoint", False):
+            StripNDSolver._no_transpose(self)
+        return getattr(super(StripNDSolver, self), name)(*a, **kw)
+    method.__name__ = name
+    method.__qualname__ = "StripNDSolver." + name
+    method.__doc__ = f"{name} of the solve driver, served only with adjoint=True (else NotImplementedError)."
+    return method
+
+
+for _name in ("solve_T", "solve1_T", "_solve_lines_T", "capture_T", "check_refinement_T"):
+    setattr(StripNDSolver, _name, _adjoint_only(_name))
+del _name

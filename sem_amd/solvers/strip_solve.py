@@ -29,8 +29,9 @@ by the transposed block-Thomas sweeps, and the transposed interior back substitu
 The reduced system over the strip-boundary lines (step 3 and the solve's all-gather + GEMV) and the agreed graph
 capture live in `_StripReduced`, which the NS velocity solve's default strip solver shares:
 nested_dissection.StripNDSolver eliminates each strip by nested dissection instead of by lines and hands the same
-reduced system its Schur complement on the strip's two interface lines.  StripLineSolver stays the strip solver of
-the other Dirichlet sets (the CD Jacobian's W / E rows).
+reduced system its Schur complement on the strip's two interface lines -- and, built with adjoint=True, the transposed
+reduced solve (_reduced_solve_T) between the two halves of its transposed steps.  StripLineSolver stays the strip
+solver of the other Dirichlet sets (the CD Jacobian's W / E rows).
 """
 import os
 
