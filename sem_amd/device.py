@@ -417,7 +417,7 @@ def no_gc():
     finaliser of an unrelated object (an old hipGraph, a mesh handle) whose device calls are illegal
     while the stream captures, which aborts the process.  torch.cuda.graph collects on entry (an
     explicit gc.collect runs while the GC is disabled); enter no_gc() first so that the capture has
-    ended before collection is enabled again: `with no_gc(), torch.cuda.graph(g): ...`."""
+    ended before collection is enabled again, as CapturedOp does."""
     enabled = gc.isenabled()
     gc.disable()
     try:
@@ -427,22 +427,63 @@ def no_gc():
             gc.enable()
 
 
-def capture_graph(device, fn):
-    """Capture fn() in a hipGraph: one call of fn on a side stream first (the warm-up outside the capture: library
-    workspaces, lazily built tables), then the capture on the current stream under no_gc().  Returns (graph, fn's
-    output inside the capture); (None, None) after a synchronise when the device libraries refuse, and the
-    caller stays eager.  fn must read its input from a buffer that lives as long as the graph."""
-    cur = torch.cuda.current_stream(device)
-    s = torch.cuda.Stream(device)
-    s.wait_stream(cur)
-    try:
-        with torch.cuda.stream(s):
-            fn()
-        cur.wait_stream(s)
+class CapturedOp:
+    """v -> fn(v), replayed from a hipGraph when one could be captured: the package's one capture path (the line
+    solves of both directions and the four Schur operators).  `graph` is the hipGraph or None (eager), `x` and `out`
+    its input and output buffers: op(v) copies v into x, replays and returns a clone of out (v is left alone); a
+    caller may instead fill views of x, replay `graph` and read views of out itself.
+
+    Nothing is captured, and `agree` is never called, unless `capture` is true and the device is a GPU.  Otherwise:
+    x (float64, `shape`) is filled with a probe seeded by `seed`; fn(x) runs once on a side stream (the warm-up outside
+    the capture: library workspaces, lazily built tables, communicators), and its result is the eager reference; then
+    fn(x) is captured on the current stream under no_gc().  A RuntimeError (the device libraries refuse) is followed by
+    a synchronise and counts as not captured.  A capture executes no collective, so a rank whose capture fails
+    desynchronises no other rank.
+    agree(ok) -> bool, the same answer on every rank (parallel.all_agree), is for an fn with collectives in it, whose
+    graph must be used by every rank or by none: agree(captured); if yes every rank copies the probe into x, replays
+    (the collectives need every rank) and compares out with the warm-up's result in the relative max norm, and
+    agree(error <= 1e-12) decides.  Without agree the graph is used as captured."""
+
+    def __init__(self, device, fn, shape, *, capture=True, agree=None, seed=0):
+        self.fn = fn
+        self.graph = self.x = self.out = None
+        device = torch.device(device)
+        if not capture or device.type != "cuda":
+            return
+        self.x = torch.rand(shape, dtype=torch.float64, device=device,
+                            generator=torch.Generator(device=device).manual_seed(seed))
+        probe = self.x.clone()
+        # The error mode of every capture is decided here.  A process group's watchdog thread (ProcessGroupNCCL) polls
+        # the events of earlier collectives -- the warm-up's -- while this thread captures; in "global" mode another
+        # thread's HIP call during a capture is an error that ends the process, in "thread_local" mode it is not.
+        pg = torch.distributed.is_available() and torch.distributed.is_initialized()
+        cur = torch.cuda.current_stream(device)
+        side = torch.cuda.Stream(device)
+        side.wait_stream(cur)
         g = torch.cuda.CUDAGraph()
-        with no_gc(), torch.cuda.graph(g):
-            out = fn()
-        return g, out
-    except RuntimeError:
-        torch.cuda.synchronize(device)
-        return None, None
+        try:
+            with torch.cuda.stream(side):
+                want = fn(self.x)
+            cur.wait_stream(side)
+            with no_gc(), torch.cuda.graph(g, capture_error_mode="thread_local" if pg else "global"):
+                out = fn(self.x)
+            ok = True
+        except RuntimeError:
+            torch.cuda.synchronize(device)
+            ok = False
+        if agree is not None:
+            ok = agree(ok)
+            if ok:
+                self.x.copy_(probe)
+                g.replay()
+                err = (out - want).abs().max() / want.abs().max().clamp(min=1e-300)
+                ok = agree(bool(err <= 1e-12))
+        if ok:
+            self.graph, self.out = g, out
+
+    def __call__(self, v):
+        if self.graph is None:
+            return self.fn(v)
+        self.x.copy_(v)
+        self.graph.replay()
+        return self.out.clone()

@@ -24,6 +24,14 @@ sums, and a + b == b + a in IEEE arithmetic).
 import torch
 
 
+def all_agree(dist, group, device, ok):
+    """True when every rank of `group` reports ok: one MIN all-reduce of a one-element float64 flag on `device`, where
+    the collectives' buffers live.  Every rank gets the same answer, so every rank takes the same decision."""
+    flag = torch.tensor([1.0 if ok else 0.0], dtype=torch.float64, device=device)
+    dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=group)
+    return float(flag.item()) == 1.0
+
+
 class StripPartition:
     def __init__(self, nex, world):
         if world < 1 or world > nex:

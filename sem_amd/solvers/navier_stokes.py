@@ -25,9 +25,10 @@ import numpy as np
 import torch
 
 from .. import SEM, _lib
-from ..device import capture_graph, get_mesh, mass_diagonal, no_gc
+from ..device import CapturedOp, get_mesh, mass_diagonal
 from ..krylov import Recycle, gcro, gmres
 from ..operators import ConvectionTensor, SEMOperator
+from ..parallel import all_agree
 from ..tracing import phase
 from ._base import SolverBase
 from .convection_diffusion import DirichletRows
@@ -471,14 +472,7 @@ class NavierStokesSolver(SolverBase):
         vs = self._strip_velocity_solver()
         if not isinstance(vs, StripNDSolver):
             raise ValueError(_NEEDS_ND)
-        if vs._apply_T is None:
-            p = self._part
-            vs.set_operator(self._velocity_apply_lines, amax=lambda t: p.amax(t),
-                            apply_lines_T=self._velocity_apply_lines_T)
-            vs.check_refinement_T()
-            if self._velocity_graph:
-                vs.capture_T()
-        return vs
+        return self._ready_T(vs, amax=self._part.amax)
 
     def _velocity_solver_T(self):
         """_velocity_solver()'s factor made ready for transposed solves: the first call after a linearisation
@@ -487,8 +481,14 @@ class NavierStokesSolver(SolverBase):
         vs = self._velocity_solver()
         if not isinstance(vs, NestedDissectionSolver):
             raise ValueError(_NEEDS_ND)
+        return self._ready_T(vs)
+
+    def _ready_T(self, vs, amax=None):
+        """The first call after a linearisation registers the transposed operator on the velocity factor vs (amax:
+        set_operator's, the strips' reduced max norm), runs check_refinement_T and, with velocity_graph, attempts
+        capture_T; returns vs."""
         if vs._apply_T is None:
-            vs.set_operator(self._velocity_apply_lines, apply_lines_T=self._velocity_apply_lines_T)
+            vs.set_operator(self._velocity_apply_lines, amax=amax, apply_lines_T=self._velocity_apply_lines_T)
             vs.check_refinement_T()
             if self._velocity_graph:
                 vs.capture_T()
@@ -752,67 +752,60 @@ class NavierStokesSolver(SolverBase):
                                                                                                          points_plot)
 
 
-class _StripSchur:
+class _SchurComplement:
+    """The pressure Schur-complement operator of _get_update (NavierStokes_Solver.py:194-203):
+    S dp = dres_cont(-J^-1 [G_x dp; G_y dp]_D, dp), i.e. two fused sem_ns_apply launches around one
+    velocity solve.  The gradients are written straight into the solve's line-interleaved [u | v]
+    layout and the divergence reads the solution from it (uv_pitch = 2 N_y), and the whole matvec is
+    captured in one hipGraph per linearisation: a Krylov iteration then costs one graph launch.
+    The base of the four Schur operators: a subclass gives _body (one matvec, eager) and, where its rules differ,
+    _capture_kw; the capture, the eager fallback and the replay are device.CapturedOp's."""
+
+    def __init__(self, ns, vs, graph=True):
+        self.ns, self.vs = ns, vs
+        m = ns._mesh
+        # the [u | v] line buffer the bodies write into (all but _StripSchur's, which stacks plain vectors)
+        self._B = torch.zeros((m.n_local // m.NY, 2 * m.NY), dtype=torch.float64, device=m.device)
+        self._op = CapturedOp(m.device, self._body, m.n_local, **self._capture_kw(graph))
+
+    _graph = property(lambda self: self._op.graph)
+    _x = property(lambda self: self._op.x)
+    _out = property(lambda self: self._op.out)
+
+    def _capture_kw(self, graph):
+        return dict(capture=graph and (self.vs.P == 1 or self.vs.interior != "lu"))
+
+    def _body(self, dp):
+        ns, m, NY = self.ns, self.ns._mesh, self.ns._mesh.NY
+        B = self._B
+        m.ns_apply(None, None, dp, B[:, :NY], B[:, NY:], **ns._ns_kw(pin_first=False))
+        X = self.vs._solve_lines(B)
+        rc = torch.empty_like(dp)
+        m.ns_apply(X[:, :NY], X[:, NY:], dp, rc=rc, c_div=-1.0, **ns._ns_kw(pin_first=False))
+        return rc
+
+    def __call__(self, dp):
+        return self._op(dp)
+
+
+class _StripSchur(_SchurComplement):
     """The strip-partitioned Schur-complement operator (_schur_strips: gradient launch + interface assembly,
     the element-partitioned velocity solve with its all-gather, divergence launch + assembly).  Under RCCL
     every step stays on the device (collectives included), so the whole matvec is captured in one hipGraph
     per linearisation, as the whole-mesh _SchurComplement is; the capture is used only after its replay has
-    reproduced the eager matvec on a probe vector, and every rank takes the same decision.  Under gloo (the
-    CPU rehearsal, host-staged collectives) the matvec stays eager."""
+    reproduced the eager matvec on a probe vector, and every rank takes the same decision (CapturedOp's agreed
+    capture).  Under gloo (the CPU rehearsal, host-staged collectives) the matvec stays eager."""
 
-    def __init__(self, ns, vs, graph=True):
-        self.ns, self.vs = ns, vs
-        m, part = ns._mesh, ns._part
-        self._graph = None
+    def _capture_kw(self, graph):
         # SEM_STRIP_GRAPH=0 keeps the matvec eager (ADVICE r4: the capture of RCCL collectives is checked against
         # the eager matvec on a probe vector, but no multi-GPU run has exercised it yet -- DESIGN.md section 7)
-        if (graph and m.device.type == "cuda" and part.backend_device().type == "cuda"
-                and os.environ.get("SEM_STRIP_GRAPH", "1") != "0"):
-            self._capture()
-
-    def _capture(self):
-        ns, m, part = self.ns, self.ns._mesh, self.ns._part
-        dev = m.device
-        g0 = torch.Generator(device=dev).manual_seed(5)
-        probe = torch.rand(m.n_local, dtype=torch.float64, device=dev, generator=g0)
-        self._x = torch.zeros_like(probe)
-        cur = torch.cuda.current_stream(dev)
-        s = torch.cuda.Stream(dev)
-        s.wait_stream(cur)
-        with torch.cuda.stream(s):
-            want = self._body(probe)   # warm-up outside the capture (workspaces, communicators)
-        cur.wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        try:   # a capture executes no collective, so a rank whose capture fails cannot desynchronise the others
-            with no_gc(), torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self._out = self._body(self._x)
-            ok = 1.0
-        except RuntimeError:
-            torch.cuda.synchronize(dev)
-            ok = 0.0
-        if self._agree(ok):    # every rank captured: replay (its collectives need every rank) and compare
-            self._x.copy_(probe)
-            g.replay()
-            err = (self._out - want).abs().max() / want.abs().max().clamp(min=1e-300)
-            if self._agree(1.0 if bool(err <= 1e-12) else 0.0):
-                self._graph = g
-
-    def _agree(self, ok):
-        """True when every rank reports ok (one all-reduce)."""
         part = self.ns._part
-        flag = torch.tensor([ok], dtype=torch.float64, device=self.ns._mesh.device)
-        part.dist.all_reduce(flag, op=part.dist.ReduceOp.MIN, group=part.group)
-        return float(flag.item()) == 1.0
+        dev = part.backend_device()
+        return dict(capture=graph and dev.type == "cuda" and os.environ.get("SEM_STRIP_GRAPH", "1") != "0",
+                    agree=lambda ok: all_agree(part.dist, part.group, dev, ok), seed=5)
 
     def _body(self, dp):
         return self.ns._schur_strips(self.vs, dp)
-
-    def __call__(self, dp):
-        if self._graph is None:
-            return self._body(dp)
-        self._x.copy_(dp)
-        self._graph.replay()
-        return self._out.clone()
 
 
 class _StripSchurT(_StripSchur):
@@ -823,12 +816,6 @@ class _StripSchurT(_StripSchur):
     both components of both lines, one collective, one unpack); the transposed strip solve runs on it; the
     transposed-divergence launch reads the solution's line views and writes yp, assembled as a plain vector.  No
     field is stacked into or reshaped out of the line layout."""
-
-    def __init__(self, ns, vs, graph=True):
-        m = ns._mesh
-        lines = m.n_local // m.NY
-        self._B = torch.zeros((lines, 2 * m.NY), dtype=torch.float64, device=m.device)
-        super().__init__(ns, vs, graph=graph)
 
     def _body(self, q):
         ns, m, part, NY = self.ns, self.ns._mesh, self.ns._part, self.ns._mesh.NY
@@ -846,42 +833,6 @@ class _StripSchurT(_StripSchur):
         with phase("schur_T.div_assemble"):
             part.assemble(yp)
         return yp
-
-
-class _SchurComplement:
-    """The pressure Schur-complement operator of _get_update (NavierStokes_Solver.py:194-203):
-    S dp = dres_cont(-J^-1 [G_x dp; G_y dp]_D, dp), i.e. two fused sem_ns_apply launches around one
-    velocity solve.  The gradients are written straight into the solve's line-interleaved [u | v]
-    layout and the divergence reads the solution from it (uv_pitch = 2 N_y), and the whole matvec is
-    captured in one hipGraph per linearisation: a Krylov iteration then costs one graph launch."""
-
-    def __init__(self, ns, vs, graph=True):
-        self.ns, self.vs = ns, vs
-        m = ns._mesh
-        self._B = torch.zeros((m.NX, 2 * m.NY), dtype=torch.float64, device=m.device)
-        self._x = torch.zeros(m.n_local, dtype=torch.float64, device=m.device)
-        self._graph = None
-        if graph and m.device.type == "cuda" and (vs.P == 1 or vs.interior != "lu"):
-            self._capture()
-
-    def _body(self, dp):
-        ns, m, NY = self.ns, self.ns._mesh, self.ns._mesh.NY
-        B = self._B
-        m.ns_apply(None, None, dp, B[:, :NY], B[:, NY:], **ns._ns_kw(pin_first=False))
-        X = self.vs._solve_lines(B)
-        rc = torch.empty_like(dp)
-        m.ns_apply(X[:, :NY], X[:, NY:], dp, rc=rc, c_div=-1.0, **ns._ns_kw(pin_first=False))
-        return rc
-
-    def _capture(self):
-        self._graph, self._out = capture_graph(self.ns._mesh.device, lambda: self._body(self._x))
-
-    def __call__(self, dp):
-        if self._graph is None:
-            return self._body(dp)
-        self._x.copy_(dp)
-        self._graph.replay()
-        return self._out.clone()
 
 
 class _SchurComplementT(_SchurComplement):

@@ -37,6 +37,7 @@ import os
 
 import torch
 
+from ..parallel import all_agree
 from ..tracing import phase
 from .velocity_solve import (VelocityJacobianSolver, _gemv, _gemv2, _gemv2_t, _gemv_t, fused_thomas_operators,
                              fused_thomas_solve, fused_thomas_solve_T, pivot_inverse, twisted_thomas_operators,
@@ -185,28 +186,15 @@ class _StripReduced:
     def _capture_agreed(self, s):
         """Graph capture of the solve of direction s ("" or "_T"): only when the reduced system's collective runs on
         the device (RCCL, capturable); under gloo it goes through the host, so the solve stays eager.
-        Under RCCL the captured graph is checked against the eager solve before it is used."""
+        Under RCCL the graph is used only when every rank captured it and its replay reproduced the eager solve on a
+        probe (device.CapturedOp's agreed capture).  The inherited capture's own refusals are the same on every rank
+        and need no agreement."""
         if self.G > 1 and (self.gather_device.type != "cuda" or os.environ.get("SEM_STRIP_GRAPH", "1") == "0"):
             if s:
                 self._require_T()
             return False
-        captured = getattr(super(), "capture" + s)()   # a capture executes no collective: a failure desynchronises no rank
-        if self.G == 1:
-            return captured
-        if not self._agree(captured):
-            setattr(self, "_graph" + s, None)
-            return False
-        bin_, graph = getattr(self, "_bin" + s), getattr(self, "_graph" + s)
-        g = torch.Generator(device=self.device).manual_seed(11)
-        b = torch.rand(bin_.shape, dtype=torch.float64, device=self.device, generator=g)
-        want = getattr(self, "_solve_lines" + s)(b.clone())
-        bin_.copy_(b)
-        graph.replay()                 # every rank replays: its collective needs every rank
-        err = (getattr(self, "_xout" + s) - want).abs().max() / want.abs().max().clamp(min=1e-300)
-        if not self._agree(bool(err <= 1e-12)):
-            setattr(self, "_graph" + s, None)
-            return False
-        return True
+        agree = None if self.G == 1 else (lambda ok: all_agree(self.dist, self.group, self.gather_device, ok))
+        return getattr(super(), "capture" + s)(agree=agree, seed=11)
 
     def capture(self):
         return self._capture_agreed("")
@@ -214,12 +202,6 @@ class _StripReduced:
     def capture_T(self):
         """capture's twin for the transposed solve, under the same rules."""
         return self._capture_agreed("_T")
-
-    def _agree(self, ok):
-        """True when every rank reports ok (one all-reduce; every rank takes the same decision)."""
-        flag = torch.tensor([1.0 if ok else 0.0], dtype=torch.float64, device=self.gather_device)
-        self.dist.all_reduce(flag, op=self.dist.ReduceOp.MIN, group=self.group)
-        return float(flag.item()) == 1.0
 
 
 class StripLineSolver(_StripReduced, VelocityJacobianSolver):

@@ -29,7 +29,7 @@ import time
 
 import torch
 
-from ..device import capture_graph
+from ..device import CapturedOp
 from ..tracing import phase
 
 GEMV_LDS_DOUBLES = 8192   # sem_block_gemv stages S m operand doubles in LDS (include/sem_ops.h)
@@ -1559,16 +1559,15 @@ class VelocityJacobianSolver:
         setattr(self, "refine" + s, eta > tau)
         return eta
 
-    def _capture(self, s):
+    def _capture(self, s, **kw):
         """Capture the direction's line solve (refinement step included) in a hipGraph of its own, with its own input
-        and output buffers; False, and the solve stays eager, when the device libraries refuse the capture."""
-        b = torch.zeros((self.NX, self.m), dtype=torch.float64, device=self.device)
-        solve = getattr(self, "_solve_lines" + s)
-        setattr(self, "_bin" + s, b)
-        g, out = capture_graph(self.device, lambda: solve(b))
-        setattr(self, "_graph" + s, g)
-        setattr(self, "_xout" + s, out)
-        return g is not None
+        and output buffers (device.CapturedOp; kw: its agree and seed); False, and the solve stays eager, off the GPU
+        and when the capture is refused."""
+        op = CapturedOp(self.device, getattr(self, "_solve_lines" + s), (self.NX, self.m), **kw)
+        setattr(self, "_bin" + s, op.x)
+        setattr(self, "_graph" + s, op.graph)
+        setattr(self, "_xout" + s, op.out)
+        return op.graph is not None
 
     def _solve_vectors(self, s, name, parts):
         """The direction's solve of length-N vectors in the x-major numbering, one per component: packed into the line
@@ -1599,15 +1598,15 @@ class VelocityJacobianSolver:
         """The backward-error gate of the forward solve (_gate): sets refine and refine_eta, returns eta."""
         return self._gate("", tau, seed)
 
-    def capture(self):
+    def capture(self, **kw):
         """Capture the solve (about 3 (N_ex+1) + 10 launches) in a hipGraph: a Schur-complement
         matvec then costs the kernels, not the Python and launch overhead of that many small ops.
-        Returns False (and the solve stays eager) if the device libraries refuse the capture."""
+        Returns False (and the solve stays eager) if the device libraries refuse the capture.  kw: _capture's."""
         if self.device.type != "cuda" or not self.factored:
             return False
         if self.P > 1 and self.interior == "lu":
             return False   # the batched LU solve (rocSOLVER getrs) cannot be stream-captured
-        return self._capture("")
+        return self._capture("", **kw)
 
     def solve(self, bu, bv):
         """(J^-1 [bu; bv]) split as (xu, xv); bu, bv are length-N vectors in the x-major numbering."""
@@ -1628,10 +1627,10 @@ class VelocityJacobianSolver:
         self._require_T()
         return self._gate("_T", tau, seed)
 
-    def capture_T(self):
+    def capture_T(self, **kw):
         """capture's twin: solve_T / solve1_T replay a graph of their own.  Returns False off the GPU."""
         self._require_T()
-        return self.device.type == "cuda" and self._capture("_T")
+        return self._capture("_T", **kw)
 
     def solve_T(self, bu, bv):
         """(J^-T [bu; bv]) split as (xu, xv), from the forward factor."""
